@@ -6,13 +6,19 @@ whole-job throughput with the graph already resident in HBM: one "step" = one co
 job on the device (init baskets + 30 iterations of the basket merge + final top-K).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--scale 22] [--K 64] [--L 128] [--iters 30]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the JSON line. --dump-outputs DIR also
+writes what the last timed step computed (DIR/*.npy, see dump_outputs). --full adds the legs that
+take runs of their own: cpu_baseline and end_to_end below (--no-cpu-baseline / --no-e2e drop one).
 
 N > 1 (torch.distributed.run, one rank per GPU over RCCL): every rank holds the graph and a
 slab replica, merges a contiguous shard of each iteration's active sources, and the updated
 basket rows are all-gathered (approximated_personalized_pagerank_amd/shard.py).
 value = |V| * steps / max-over-ranks time; scaling "strong" (the job is fixed, sources split).
 
-Extra objects on the JSON line (DESIGN.md "measurement"):
+Extra objects on the JSON line (DESIGN.md "measurement"; cpu_baseline and end_to_end are null
+without --full):
   roofline      merge phase: SURVEY s8d algorithmic bytes / merge-phase time (hipEvents on the
                 plan's stream), against 8 TB/s HBM
   end_to_end    the reference's API end to end (tests/cpp/dropin_test.cc: unordered_map graph in,
@@ -179,6 +185,30 @@ def end_to_end(scale, iters, K, L):
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET = 48 << 20  # bytes of .npy per dump (the files stay well under 64 MB in all)
+
+
+def dump_outputs(path, res, seed=0):
+    """--dump-outputs: the top-K result of the last timed step as a caller receives it from
+    plan.fetch() (ids [n, K], scores [n, K], lens [n]), as float64 .npy files under `path`. A result
+    past DUMP_BUDGET is sampled by rows: a fixed choice (default_rng(seed), sorted) that depends on
+    n and K only, so two builds run with the same arguments dump the same rows; rows.npy names
+    them. Entries past a row's length are written as id -1 / score 0."""
+    n, K = res.ids.shape
+    keep = int(DUMP_BUDGET // (16 * K + 16))
+    rows = np.arange(n) if n <= keep else np.sort(np.random.default_rng(seed).choice(n, keep, replace=False))
+    lens = res.lens[rows]
+    pad = np.arange(K)[None, :] >= lens[:, None]
+    ids = res.ids[rows].astype(np.float64)
+    sc = res.scores[rows].astype(np.float64)
+    ids[pad] = -1.0
+    sc[pad] = 0.0
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("rows", rows.astype(np.float64)), ("ids", ids), ("scores", sc), ("lens", lens.astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), a)
+    log(f"dumped {len(rows)} of {n} result rows to {path}")
 
 
 def host_cpus():
@@ -353,8 +383,10 @@ def main_mc(args):
         comb_ms += st.combine_ms
     elapsed = time.perf_counter() - t0
     steps = args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, plan.fetch())
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         try:
             plan.close()
             cpu = mc_cpu_baseline(max(8, args.scale - 6), K, L, args.walks, args.damping, args.seed)
@@ -392,12 +424,20 @@ def main():
     ap.add_argument("--cpu-threads", type=int, default=0,
                     help="cpu_baseline threads (0 = every host CPU this process may use, cgroup quota included)")
     ap.add_argument("--cpu-budget", type=float, default=1.5e9, help="sampled candidates for cpu_baseline")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the end_to_end leg (reference-API call)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the legs that take runs of their own: cpu_baseline and end_to_end")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-e2e", action="store_true", help="with --full: skip the end_to_end leg (reference-API call)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the result of the last timed step as DIR/<name>.npy (one GPU)")
     ap.add_argument("--workload", choices=["grank", "mc"], default="grank",
                     help="mc: MCCompletePathV2 (configs[4]) with --K 50 --L 200 --walks 1000 defaults")
     ap.add_argument("--walks", type=int, default=1000, help="mc: random walks per node (R)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        ap.error("--dump-outputs writes the result of a one-GPU run")
     if args.workload == "mc":
         return main_mc(args)
 
@@ -445,8 +485,10 @@ def main():
         elapsed = time.perf_counter() - t0
         stats = dict(merge_ms=merge_ms, algo_bytes=algo, device_ms=dev_ms, iterations=st.iterations_run,
                      launches=launches, kernels=kst)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, plan.fetch())
         cpu = e2e = None
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             try:
                 slab = plan.fetch_slab()
                 plan.close()
@@ -456,7 +498,7 @@ def main():
                 log(f"cpu_baseline failed: {exc!r}")
                 cpu = None
         plan.close()
-        if not args.no_e2e:
+        if args.full and not args.no_e2e:
             try:
                 e2e = end_to_end(args.scale, args.iters, args.K, args.L)
             except Exception as exc:  # reported, never fatal

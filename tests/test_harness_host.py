@@ -37,6 +37,42 @@ def test_kendall_is_tau_b():
         assert kendall_correlation(x, y) == pytest.approx(ref, abs=1e-12)
 
 
+def _bench():
+    import importlib.util
+    import os
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(os.path.dirname(__file__), "..", "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    return bench
+
+
+@pytest.mark.parametrize("n", [100, 9001])
+def test_bench_dump_outputs_rows_and_padding(n, tmp_path, monkeypatch):
+    """bench.py --dump-outputs: float64 .npy files of the fetched top-K; a result past the byte
+    budget is cut to a fixed, sorted row sample that rows.npy names (the same rows on every call),
+    and entries past a row's length come out as id -1 / score 0 whatever the buffers held."""
+    from approximated_personalized_pagerank_amd import GrankResult
+    bench = _bench()
+    K = 8
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1000 * (16 * K + 16))
+    rng = np.random.default_rng(n)
+    res = GrankResult(rng.integers(0, n, (n, K)).astype(np.int32), rng.random((n, K)),
+                      rng.integers(0, K + 1, n).astype(np.int32))
+    bench.dump_outputs(str(tmp_path / "a"), res)
+    bench.dump_outputs(str(tmp_path / "b"), res)
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("rows", "ids", "scores", "lens")}
+    for k, v in a.items():
+        assert v.dtype == np.float64
+        assert np.array_equal(v, np.load(tmp_path / "b" / f"{k}.npy"))
+    rows = a["rows"].astype(np.int64)
+    assert len(rows) == min(n, 1000) and np.all(np.diff(rows) > 0) and rows[-1] < n
+    assert sum(v.nbytes for v in a.values()) <= 1000 * (16 * K + 16)
+    assert np.array_equal(a["lens"], res.lens[rows])
+    live = np.arange(K)[None, :] < res.lens[rows][:, None]
+    assert np.array_equal(a["ids"][live], res.ids[rows][live]) and np.array_equal(a["scores"][live], res.scores[rows][live])
+    assert np.all(a["ids"][~live] == -1) and np.all(a["scores"][~live] == 0)
+
+
 def test_bench_kernel_groups_share_the_phase():
     """bench.py's per-kernel roofline: the group shares sum to the merge phase (never past it), the
     one-slice sieve classes fold into one group, and the dominant group is the largest share."""

@@ -8,7 +8,7 @@ import pytest
 
 import approximated_personalized_pagerank_amd as ppr
 from approximated_personalized_pagerank_amd import _lib
-from helpers import all_names, load
+from helpers import GOLDEN, all_names, load
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -113,10 +113,14 @@ def test_import_edge_csv_semantics(tmp_path):
     assert g.m == 5
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/example.txt"), reason="reference tree absent")
-def test_import_edge_csv_reference_order_eat():
-    # the reference's own iteration order of example.txt (recorded in the g4 fixture by ref_driver)
-    g = ppr.import_edge_csv("/root/reference/example.txt")
+def test_import_edge_csv_reference_order_eat(tmp_path):
+    # the reference's own iteration order of example.txt (recorded in the g4 fixture by ref_driver);
+    # the edge list itself is stored compressed beside it (tests/golden/eat_example.txt.xz)
+    import lzma
+    p = tmp_path / "example.txt"
+    with lzma.open(os.path.join(GOLDEN, "eat_example.txt.xz")) as f:
+        p.write_bytes(f.read())
+    g = ppr.import_edge_csv(str(p))
     f = load("g4_eat_k50_l100")
     assert np.array_equal(np.array(g.keys), f["z"]["order"])
     assert np.array_equal(g.row_ptr, f["rp"]) and np.array_equal(g.col, f["col"])

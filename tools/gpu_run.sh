@@ -24,7 +24,7 @@ for step in "$@"; do
       timeout -k 10 900 python -u -m pytest tests -m gpu -x -q --timeout 240 --timeout-method thread ${k:+-k "$k"} \
         > "$out/pytest.txt" 2>&1 || { echo "tests failed rc=$?"; tail -30 "$out/pytest.txt"; exit 1; } ;;
     bench)
-      extra="--no-cpu-baseline --no-e2e"; [ "${FULL:-0}" = 1 ] && extra=""
+      extra=""; [ "${FULL:-0}" = 1 ] && extra="--full"
       timeout -k 10 600 python -u bench.py --steps ${STEPS:-3} --warmup 1 $extra > "$out/bench.json" 2> "$out/bench.err" \
         || { echo "bench failed rc=$?"; tail -20 "$out/bench.err"; exit 1; }
       cat "$out/bench.json" ;;

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/${1:-final}
 mkdir -p $OUT
 if [ -z "$SKIP_BENCH" ]; then
-  timeout -k 10 500 python3 bench.py > $OUT/bench.json 2> $OUT/bench.err
+  timeout -k 10 500 python3 bench.py --full > $OUT/bench.json 2> $OUT/bench.err
   echo bench done
 fi
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -d $OUT/trace -o run -- python3 bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-e2e > $OUT/trace.json 2> $OUT/trace.err
