@@ -277,6 +277,10 @@ struct ppr_plan {
   int64_t sv_sources = 0, sv_redo = 0;  // sieved sources, handed back after an overflow (PPR_TIMING)
   int64_t sv_redo_dev = 0;            // small / mid-class overflows redone on the device (mid / large geometry)
   double xh_s[8] = {};                // run_xhubs host sections, s (PPR_TIMING at destroy)
+  // preference-set queries (query.hip): grow-only scratch of one chunk, kept across calls
+  unsigned char* d_q = nullptr;       // query arrays, planner verdicts, tier lists, outputs
+  unsigned char* d_ql = nullptr;      // range tasks and their appended lists
+  size_t q_bytes = 0, ql_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -329,6 +333,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_xg);
   hipFree(p->d_wovl);
   hipFree(p->d_wl);
+  hipFree(p->d_q); hipFree(p->d_ql);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (getenv("PPR_TIMING") && p->sv_sources)

@@ -501,12 +501,21 @@ __device__ __forceinline__ void radix_kth_desc(int n, int& k, GetV getv, Filt fi
 struct SelAll {
   __device__ bool operator()(int) const { return true; }
 };
+// Tie weight of the selections below (larger = preferred): the per-source hash of an iterated top-L
+// (the default, see tie_w), or the dense id ascending -- the plain output order, for a selection
+// whose result feeds nothing back (query.h).
+struct TieHash {
+  __device__ uint32_t operator()(int key, uint32_t ts) const { return tie_w(key, ts); }
+};
+struct TieIdAsc {
+  __device__ uint32_t operator()(int key, uint32_t) const { return ~(uint32_t)key; }
+};
 #ifndef PPR_SEL_REG
 #define PPR_SEL_REG 1  // (A/B only: 0 = the histogram passes for every size)
 #endif
-template <class KeyAt, class ValAt, class Occ = SelAll>
+template <class KeyAt, class ValAt, class Occ = SelAll, class TieW = TieHash>
 __device__ __forceinline__ SelCrit select_top_reg(int n, int need, KeyAt keyat, ValAt valat, uint32_t ts,
-                                                  Occ occ = Occ{}) {
+                                                  Occ occ = Occ{}, TieW tw = TieW{}) {
   constexpr int R = 4;
   uint64_t v[R];
   bool ok[R];
@@ -555,7 +564,7 @@ __device__ __forceinline__ SelCrit select_top_reg(int n, int need, KeyAt keyat, 
 #pragma unroll
     for (int j = 0; j < R; j++) {
       eq[j] = ok[j] && v[j] == x;
-      w[j] = eq[j] ? tie_w(keyat(j * WAVE + lane_id()), ts) : 0u;
+      w[j] = eq[j] ? tw(keyat(j * WAVE + lane_id()), ts) : 0u;
       if (eq[j]) { wor |= w[j]; wand &= w[j]; }
     }
     wor = (uint32_t)wave_or(wor);
@@ -583,10 +592,10 @@ __device__ __forceinline__ SelCrit select_top_reg(int n, int need, KeyAt keyat, 
   return c;
 }
 
-template <class KeyAt, class ValAt>
+template <class KeyAt, class ValAt, class TieW = TieHash>
 __device__ __forceinline__ SelCrit select_top(int n, int need, KeyAt keyat, ValAt valat,
-                                              uint32_t* hist, uint32_t ts) {
-  if (PPR_SEL_REG && n <= 4 * WAVE) return select_top_reg(n, need, keyat, valat, ts);
+                                              uint32_t* hist, uint32_t ts, TieW tw = TieW{}) {
+  if (PPR_SEL_REG && n <= 4 * WAVE) return select_top_reg(n, need, keyat, valat, ts, SelAll{}, tw);
   SelCrit c;
   c.tie = false; c.pb = 0; c.mb = 0;
   int k = need;
@@ -597,7 +606,7 @@ __device__ __forceinline__ SelCrit select_top(int n, int need, KeyAt keyat, ValA
     // all boundary entries carry exactly the same score: keep the k with the largest tie_w
     const uint64_t pa = c.pa;
     bool tie2 = false;
-    radix_kth_desc(n, k, [&](int i) { return (uint64_t)tie_w(keyat(i), ts); },
+    radix_kth_desc(n, k, [&](int i) { return (uint64_t)tw(keyat(i), ts); },
                    [&](int i) { return dbits(valat(i)) == pa; }, hist, c.pb, c.mb, tie2);
     c.tie = true;
   }

@@ -56,6 +56,67 @@ class GrankResult:
         return out
 
 
+@dataclass
+class QueryResult:
+    """Answer of GrankPlan.query: row q = the K best (id, score) of query q's preference set."""
+    ids: np.ndarray        # int32 [Q, K] dense ids, score desc / id asc, -1 padded
+    scores: np.ndarray     # float64 [Q, K]
+    lens: np.ndarray       # int32 [Q]
+    device_ms: float = 0.0
+    candidates: int = 0
+    algo_bytes: int = 0
+    wave_queries: int = 0
+    wg_queries: int = 0
+    range_queries: int = 0
+    max_ranges: int = 0
+
+    def to_dicts(self, csr: Csr):
+        """one {graph key: score} per query, like GrankResult.to_dict's rows"""
+        return [{csr.key(int(i)): float(s) for i, s in zip(self.ids[q, :int(k)], self.scores[q, :int(k)])}
+                for q, k in enumerate(self.lens)]
+
+
+def normalize_queries(queries, weights=None):
+    """The CSR form ppr_grank_plan_query takes: (qptr int64 [Q+1], seeds int32, weights float64 or
+    None). `queries` is (qptr, seeds) arrays or a sequence of seed sequences; `weights` a flat array
+    or a sequence of sequences of the same shape. Shape mismatches raise ValueError."""
+    is_csr = (isinstance(queries, tuple) and len(queries) == 2 and isinstance(queries[0], np.ndarray)
+              and isinstance(queries[1], np.ndarray))
+    if is_csr:
+        qptr = np.ascontiguousarray(queries[0], dtype=np.int64)
+        seeds = np.ascontiguousarray(queries[1], dtype=np.int32)
+        if qptr.ndim != 1 or seeds.ndim != 1 or len(qptr) < 1 or qptr[0] != 0 or qptr[-1] != len(seeds):
+            raise ValueError("queries=(qptr, seeds): qptr must start at 0 and end at len(seeds)")
+        if np.any(np.diff(qptr) < 0):
+            raise ValueError("queries=(qptr, seeds): qptr must not decrease")
+    else:
+        rows = [np.asarray(q, dtype=np.int64).reshape(-1) for q in queries]
+        qptr = np.zeros(len(rows) + 1, dtype=np.int64)
+        if rows:
+            np.cumsum([len(r) for r in rows], out=qptr[1:])
+        flat = np.concatenate(rows) if rows else np.zeros(0, dtype=np.int64)
+        if len(flat) and (flat.min() < -2**31 or flat.max() >= 2**31):
+            raise ValueError("seed ids must fit in int32")
+        seeds = np.ascontiguousarray(flat, dtype=np.int32)
+    if weights is None:
+        return qptr, seeds, None
+    flat_w = (isinstance(weights, np.ndarray) and weights.ndim == 1 and weights.dtype != object) or (
+        not isinstance(weights, np.ndarray) and len(weights) > 0 and all(np.isscalar(x) for x in weights))
+    if flat_w:
+        w = np.ascontiguousarray(weights, dtype=np.float64)
+    else:
+        wrows = [np.asarray(r, dtype=np.float64).reshape(-1) for r in weights]
+        if len(wrows) != len(qptr) - 1:
+            raise ValueError(f"weights: {len(wrows)} rows for {len(qptr) - 1} queries")
+        for q, r in enumerate(wrows):
+            if len(r) != qptr[q + 1] - qptr[q]:
+                raise ValueError(f"weights: row {q} has {len(r)} entries for {qptr[q + 1] - qptr[q]} seeds")
+        w = np.ascontiguousarray(np.concatenate(wrows) if wrows else np.zeros(0), dtype=np.float64)
+    if len(w) != len(seeds):
+        raise ValueError(f"weights: {len(w)} entries for {len(seeds)} seeds")
+    return qptr, seeds, w
+
+
 def _stats_to(res: GrankResult, st: _lib.PprStats) -> None:
     res.iterations_run = int(st.iterations_run)
     res.max_diff = np.array(st.max_diff[: min(st.iterations_run, _lib.PPR_MAX_ITER_STATS)])
@@ -212,3 +273,26 @@ class GrankPlan:
         _lib.check(_lib.lib().ppr_grank_plan_fetch_slab(self._p, it, _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens)),
                    "fetch_slab")
         return ids, sc, lens
+
+    def query(self, queries, K: int, weights=None, exclude_seeds: bool = False,
+              iterations_run: Optional[int] = None) -> QueryResult:
+        """PageRank personalised to each query's seed set, from the plan's resident baskets
+        (include/ppr_hip.h ppr_grank_plan_query): by linearity the weighted sum of the seeds' own
+        vectors, summed exactly, the K best by (score desc, dense id asc). `queries`: (qptr, seeds)
+        arrays or a sequence of seed sequences of dense ids; `weights`: None (all 1), a flat array
+        or sequences of the same shape; `iterations_run` defaults to the plan's last run."""
+        qptr, seeds, w = normalize_queries(queries, weights)
+        Q = len(qptr) - 1
+        it = self.iterations_run if iterations_run is None else iterations_run
+        ids = np.full((Q, max(K, 0)), -1, dtype=np.int32)
+        sc = np.zeros((Q, max(K, 0)), dtype=np.float64)
+        lens = np.zeros(Q, dtype=np.int32)
+        st = _lib.PprQueryStats()
+        flags = _lib.PPR_QUERY_EXCLUDE_SEEDS if exclude_seeds else 0
+        if K < 0 or K >= 2**32:
+            raise _lib.PprError(1, "plan_query")
+        _lib.check(_lib.lib().ppr_grank_plan_query(self._p, it, Q, _lib.ptr(qptr), _lib.ptr(seeds), _lib.ptr(w), K,
+                                                   flags, _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens),
+                                                   ctypes.byref(st)), "plan_query")
+        return QueryResult(ids, sc, lens, float(st.device_ms), int(st.candidates), int(st.algo_bytes),
+                           int(st.wave_queries), int(st.wg_queries), int(st.range_queries), int(st.max_ranges))

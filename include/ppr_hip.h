@@ -231,6 +231,48 @@ void* ppr_grank_plan_stream(ppr_plan* p);
  * meaningful). MC plans: slot 0 = final baskets, slot 1 = random-walk baskets of the walk set. */
 int ppr_plan_fetch_slot(ppr_plan* p, int32_t slot, int32_t* ids, double* scores, int32_t* len);
 
+/* ---- preference-set queries from a plan's resident baskets ----
+ * No reference counterpart: the reference returns the all-sources table and leaves its use to the
+ * caller. By the linearity of PPR (Jeh & Widom) the vector personalised to a weighted set of
+ * nodes is the weighted sum of the nodes' own vectors, PPR(sum_i f_i e_{u_i}) = sum_i f_i PPR(u_i),
+ * and the plan holds those vectors in HBM: a query is one more basket merge, answered without
+ * downloading the slab.
+ * Q queries as a CSR: qptr[Q + 1] (qptr[0] = 0), seeds[qptr[Q]] (dense ids), weights[qptr[Q]] or
+ * NULL (every weight 1.0). For query q with seeds u_i and weights w_i: W = w_0 + w_1 + ... summed
+ * in seed order in fp64, f_i = w_i / W, and with B[u] the current L-wide basket of u after
+ * `iterations_run` iterations (the slot rule of ppr_grank_plan_fetch_slab)
+ *     total[k] = sum_i sum_{(k, s) in B[u_i]} floor(fl(s * f_i) * 2^93)
+ * an exact integer sum; a key's score is total * 2^-93 rounded to nearest even once. Repeated
+ * seeds add; a zero-weight seed contributes its keys with score 0 (zero scores are legal keys).
+ * Row q of out_ids / out_scores (Q * Kq) holds the Kq best (id, score) by (score desc, dense id
+ * asc) -- the same rule at the cut: a tie at the Kq-th place goes to the smaller id -- unused slots
+ * id -1 / score 0; out_len[q] = min(Kq, distinct keys). PPR_QUERY_EXCLUDE_SEEDS removes the keys
+ * that are seeds of the query (any weight) before the selection. A query without seeds gives an
+ * empty row. The result depends only on the slab and the query, not on the engine that answered
+ * it, the chunking of the call or the order of the queries.
+ * Host pointers; synchronous on the plan's stream; writes nothing into the slabs or the plan's
+ * top-K output, so a plan can be queried any number of times and run again afterwards.
+ * Errors, all decided on the host before any merge kernel starts: PPR_ERR_ARG (null plan or
+ * pointers, Q < 0, non-monotone qptr, a negative / NaN / infinite weight, a non-empty query whose
+ * W is 0 or not finite, unknown flag bits, an MC plan), PPR_ERR_K (Kq = 0), PPR_ERR_RANGE
+ * (Kq > 4096, or a query so wide that the candidates of one of its 64 key ranges exceed 3/4 of the
+ * 8192-slot table: at most 393216 candidates = sum of len[seed] when they spread evenly),
+ * PPR_ERR_SOURCE (a seed outside [0, n)).
+ * MC plans are refused: their final scores are not bounded by 1 (the combine can reach
+ * 1 / (1 - d)), so the 2^95 headroom of the 93-bit sums does not hold without a separate analysis. */
+enum { PPR_QUERY_EXCLUDE_SEEDS = 1 };
+typedef struct ppr_query_stats {
+  double device_ms;            /* hipEvents on the plan's stream: upload excluded, kernels only */
+  int64_t candidates;          /* sum of len[seed] over all seeds */
+  int64_t algo_bytes;          /* per seed 4 + 4 + 12*len[seed]; per query 12*Kq + 4 */
+  int64_t wave_queries, wg_queries, range_queries;   /* queries answered by each tier */
+  int32_t max_ranges;          /* largest key-range split used (1..64) */
+  int32_t reserved;
+} ppr_query_stats;
+int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t Q, const int64_t* qptr,
+                         const int32_t* seeds, const double* weights, uint32_t Kq, uint32_t flags,
+                         int32_t* out_ids, double* out_scores, int32_t* out_len, ppr_query_stats* st);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
