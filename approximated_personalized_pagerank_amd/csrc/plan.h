@@ -281,6 +281,11 @@ struct ppr_plan {
   unsigned char* d_q = nullptr;       // query arrays, planner verdicts, tier lists, outputs
   unsigned char* d_ql = nullptr;      // range tasks and their appended lists
   size_t q_bytes = 0, ql_bytes = 0;
+  // reverse queries (rquery.hip): the same, grow-only and kept across calls
+  unsigned char* d_r = nullptr;       // a chunk's queries, target table, postings, counts, outputs
+  unsigned char* d_rl = nullptr;      // hit lists and the levels of their reduction
+  unsigned char* d_rt = nullptr;      // reduction tasks
+  size_t r_bytes = 0, rl_bytes = 0, rt_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -334,6 +339,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_wovl);
   hipFree(p->d_wl);
   hipFree(p->d_q); hipFree(p->d_ql);
+  hipFree(p->d_r); hipFree(p->d_rl); hipFree(p->d_rt);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (getenv("PPR_TIMING") && p->sv_sources)

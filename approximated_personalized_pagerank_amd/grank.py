@@ -76,6 +76,26 @@ class QueryResult:
                 for q, k in enumerate(self.lens)]
 
 
+@dataclass
+class RQueryResult:
+    """Answer of GrankPlan.rquery: row q = the K best (source, score) for query q's target set."""
+    ids: np.ndarray        # int32 [Q, K] dense source ids, score desc / id asc, -1 padded
+    scores: np.ndarray     # float64 [Q, K]
+    lens: np.ndarray       # int32 [Q]
+    device_ms: float = 0.0
+    hits: int = 0
+    algo_bytes: int = 0
+    probe_queries: int = 0
+    scan_queries: int = 0
+    scans: int = 0
+    chunks: int = 0
+
+    def to_dicts(self, csr: Csr):
+        """one {graph key of the source: score} per query"""
+        return [{csr.key(int(i)): float(s) for i, s in zip(self.ids[q, :int(k)], self.scores[q, :int(k)])}
+                for q, k in enumerate(self.lens)]
+
+
 def normalize_queries(queries, weights=None):
     """The CSR form ppr_grank_plan_query takes: (qptr int64 [Q+1], seeds int32, weights float64 or
     None). `queries` is (qptr, seeds) arrays or a sequence of seed sequences; `weights` a flat array
@@ -296,3 +316,26 @@ class GrankPlan:
                                                    ctypes.byref(st)), "plan_query")
         return QueryResult(ids, sc, lens, float(st.device_ms), int(st.candidates), int(st.algo_bytes),
                            int(st.wave_queries), int(st.wg_queries), int(st.range_queries), int(st.max_ranges))
+
+    def rquery(self, queries, K: int, weights=None, exclude_targets: bool = False,
+               iterations_run: Optional[int] = None) -> RQueryResult:
+        """The sources that rank each query's weighted target set highest, from the plan's resident
+        baskets (include/ppr_hip.h ppr_grank_plan_rquery): score(u) = sum_j f_j B[u][t_j] over the
+        targets that are keys of u's basket, summed exactly, the K best sources by (score desc,
+        dense id asc). Arguments as for query(); `exclude_targets` drops the sources that are
+        targets of their query."""
+        qptr, targets, w = normalize_queries(queries, weights)
+        Q = len(qptr) - 1
+        it = self.iterations_run if iterations_run is None else iterations_run
+        ids = np.full((Q, max(K, 0)), -1, dtype=np.int32)
+        sc = np.zeros((Q, max(K, 0)), dtype=np.float64)
+        lens = np.zeros(Q, dtype=np.int32)
+        st = _lib.PprRQueryStats()
+        flags = _lib.PPR_RQUERY_EXCLUDE_TARGETS if exclude_targets else 0
+        if K < 0 or K >= 2**32:
+            raise _lib.PprError(1, "plan_rquery")
+        _lib.check(_lib.lib().ppr_grank_plan_rquery(self._p, it, Q, _lib.ptr(qptr), _lib.ptr(targets), _lib.ptr(w), K,
+                                                    flags, _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens),
+                                                    ctypes.byref(st)), "plan_rquery")
+        return RQueryResult(ids, sc, lens, float(st.device_ms), int(st.hits), int(st.algo_bytes),
+                            int(st.probe_queries), int(st.scan_queries), int(st.scans), int(st.chunks))

@@ -273,6 +273,50 @@ int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t Q, const i
                          const int32_t* seeds, const double* weights, uint32_t Kq, uint32_t flags,
                          int32_t* out_ids, double* out_scores, int32_t* out_len, ppr_query_stats* st);
 
+/* ---- reverse queries: the top sources of a weighted target set ----
+ * The other direction of the same resident table (no reference counterpart either): which sources
+ * rank this item, or this weighted set of items, highest -- the matrix-vector product B f, a column
+ * lookup in a table stored by rows, answered by scanning the rows' ids in HBM (or, for a handful of
+ * targets, by probing every row through its range index) instead of downloading the slab.
+ * Q queries as a CSR: qptr[Q + 1] (qptr[0] = 0), targets[qptr[Q]] (dense ids), weights[qptr[Q]] or
+ * NULL (every weight 1.0). For query q with targets t_j and weights w_j: W = w_0 + w_1 + ... summed
+ * in target order in fp64, f_j = w_j / W, and with B[u] the current L-wide basket of u after
+ * `iterations_run` iterations (the slot rule of ppr_grank_plan_fetch_slab), for every source u
+ *     X_q[u] = sum_j [t_j in B[u]] * floor(fl(B[u][t_j] * f_j) * 2^93)
+ * an exact integer sum (one fp64 multiply per term); score(u) = X_q[u] * 2^-93 rounded to nearest
+ * even once. Repeated targets add. A source is a hit of q when at least one target of q is a key of
+ * B[u]; zero scores are legal (a zero-weight target still makes its sources hits). Every row sums
+ * to <= 1 and sum f_j <= 1 + eps, so X < 2^95.
+ * Row q of out_sources / out_scores (Q * Kq) holds the Kq best hits by (score desc, source id asc)
+ * -- the same rule at the cut -- unused slots id -1 / score 0; out_len[q] = min(Kq, hits of q).
+ * PPR_RQUERY_EXCLUDE_TARGETS drops the sources that are themselves targets of the query (any
+ * weight) before the selection. A query without targets gives an empty row. The result depends
+ * only on the slab and the query: not on the tier (scan or probe), the chunking, the batching of
+ * the lists or the order of the queries.
+ * Host pointers; synchronous on the plan's stream; writes nothing into the slabs or the plan's
+ * top-K output.
+ * Errors, all decided on the host before any kernel starts: PPR_ERR_ARG (null plan or pointers,
+ * Q < 0, non-monotone qptr, a negative / NaN / infinite weight, a non-empty query whose W is 0 or
+ * not finite, unknown flag bits, an MC plan -- for the forward query's reason), PPR_ERR_K (Kq = 0),
+ * PPR_ERR_RANGE (Kq > 4096, or a single query with more targets than 3/4 of the 8192-slot target
+ * table: 6144), PPR_ERR_SOURCE (a target outside [0, n)).
+ * algo_bytes = the bytes the algorithm has to move: per pass over the slab's ids (scans)
+ * 4 * sum len[u] + 4 * n; probe tier 4 per (row, posting) for the range-index pair + 4 per id of the
+ * probed segments; per list entry (a hit source of a query) 8 for a score, 12 written and 12 read;
+ * per query 12 * Kq + 4 for its result row. */
+enum { PPR_RQUERY_EXCLUDE_TARGETS = 1 };
+typedef struct ppr_rquery_stats {
+  double device_ms;          /* HIP events around the kernels; uploads and downloads excluded */
+  int64_t hits;              /* sum over queries of hit sources */
+  int64_t algo_bytes;        /* see above */
+  int64_t probe_queries, scan_queries;   /* queries answered by each tier */
+  int64_t scans;             /* passes over the slab's ids (count and emit passes both counted) */
+  int32_t chunks; int32_t reserved;
+} ppr_rquery_stats;
+int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_t Q, const int64_t* qptr,
+                          const int32_t* targets, const double* weights, uint32_t Kq, uint32_t flags,
+                          int32_t* out_sources, double* out_scores, int32_t* out_len, ppr_rquery_stats* st);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
