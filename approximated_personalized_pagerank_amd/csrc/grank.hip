@@ -504,6 +504,10 @@ int plan_alloc(int64_t n, const int64_t* row_ptr, const int32_t* colx, uint32_t 
       p->sv_redo_large = s8 && atoi(s8) != 0;
       const char* s3 = getenv("PPR_SV_BUDGET");
       if (s3) p->sv_budget = std::max(0, std::min(SV_XT_BUDGET, atoi(s3)));
+      const char* s10 = getenv("PPR_SV_RESEED");
+      p->sv_reseed = !(s10 && atoi(s10) == 0);
+      const char* s11 = getenv("PPR_SV_RESEED_BUDGET");
+      if (s11) p->sv_reseed_budget = std::max(0, std::min(SV_XT_BUDGET, atoi(s11)));
       // Streams of the exact sum: a process has 4 hardware queues (HIP's default), and streams
       // beyond them share queues -- a kernel then waits behind another stream's kernel. The hot
       // pass's stream5 is unused here (no hot pass), so it goes, and each of the 4 remaining streams
@@ -1751,6 +1755,8 @@ struct SvRun {
   size_t o_ovl = 0;          // offset of the overflow list in d_sv
   size_t o_os = 0;           // ... and of the small class's first overflows (redone on the device)
   size_t o_om = 0;           // ... and of the mid class's (redone on the device, large geometry)
+  size_t o_cnt = 0;          // ... and of the re-seeding counters (seeded attempts, completed)
+  size_t cls_end[4] = {0, 0, 0, 0};  // descriptor index ends: multi-slice, large, mid, small
   bool live = false;
 };
 
@@ -1811,7 +1817,8 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   }
   const size_t nt = tasks.size();
   // d_sv: node ids [nx] | multi descriptors [nm] | tasks | one-slice selections (keys, values) |
-  // zeroed: ovl[1 + nx] | selected counts[nx] | oflag[nm] | gpt | gsk | gkeys | ga | gb
+  // zeroed: ovl[1 + nx] | the classes' first-overflow lists | selected counts[nx] | re-seeding counters |
+  // oflag[nm] | retry marks[nm] | seeds[nm Lp] | gpt | gsk | gkeys | ga | gb
   auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
   size_t off = 0;
   const size_t o_v = off; off = al(off + 4 * nx);
@@ -1824,8 +1831,12 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   const size_t o_ov = off; off = al(off + 4 * (1 + nx));
   const size_t o_os = off; off = al(off + 4 * (1 + nx));  // small class's first overflows (device redo)
   const size_t o_om = off; off = al(off + 4 * (1 + nx));  // mid class's first overflows (device redo)
+  const size_t o_ol = off; off = al(off + 4 * (1 + nx));  // large class's first overflows (seeded retry)
   const size_t o_sn = off; off = al(off + 4 * nx);
+  const size_t o_cn = off; off = al(off + 16);
   const size_t o_of = off; off = al(off + 4 * (nm + 1));
+  const size_t o_mk = off; off = al(off + 4 * (nm + 1));            // multi-slice: descriptors marked for the retry
+  const size_t o_sd = off; off = al(off + 4 * (size_t)Lp * (nm + 1));  // ... and their seeds (Lp a descriptor)
   const size_t o_pt = off; off = al(off + 8 * 2 * (size_t)Lp * nm);
   const size_t o_gs = off; off = al(off + 4 * (size_t)SV_R * ((size_t)1 << SV_LARGE.wlog) * nm);
   const size_t o_gk = off; off = al(off + 4 * (size_t)tg_total);
@@ -1856,6 +1867,16 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   int32_t* d_os = (int32_t*)(b + o_os);
   int32_t* d_om = (int32_t*)(b + o_om);
   int32_t* d_of = (int32_t*)(b + o_of);
+  int32_t* d_ol = (int32_t*)(b + o_ol);
+  int32_t* d_cn = (int32_t*)(b + o_cn);
+  int32_t* d_mk = (int32_t*)(b + o_mk);
+  int32_t* d_sd = (int32_t*)(b + o_sd);
+  // re-seeding (merge_sv.h SvSeed): on for a class whose first attempts hold at least Lp passing keys
+  // (a smaller table cannot improve on PT); a seeded attempt takes the budget of its geometry
+  auto seed_on = [&](const SvGeom& G) { return p->sv_reseed && std::min(p->sv_budget, G.budget) >= Lp; };
+  auto seed_budget = [&](const SvGeom& G) {
+    return std::min(p->sv_reseed_budget >= 0 ? p->sv_reseed_budget : p->sv_budget, G.budget);
+  };
   unsigned long long* d_pt = (unsigned long long*)(b + o_pt);
   uint32_t* d_sk = (uint32_t*)(b + o_gs);
   int32_t* d_ok = (int32_t*)(b + o_sk);
@@ -1888,23 +1909,32 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
       // the mid class's overflows (< 10 % of its sources; with the small class's second ones, most
       // of the host hand-backs) are redone at once with the large geometry
       const bool redo_l = c == 1 && p->sv_redo_large;
+      // the large class's overflows are retried with the same geometry, re-seeded (there is no larger
+      // one: without seeds the retry would overflow again)
+      const bool redo_s = c == 0 && seed_on(G);
+      // the list the class's first overflows go to, and (`on`) with seeds for the retry behind it
+      int32_t* first = redo ? d_os : redo_l ? d_om : redo_s ? d_ol : nullptr;
+      const int on = first && seed_on(G) ? 1 : 0;
+      const SvSeed sd1{on ? first : nullptr, d_cn, on, 0};
       hipLaunchKernelGGL(k_sv1, dim3((unsigned)cnt_c), dim3(G.threads()), sv_lds_bytes(Lp, G), cs[c], g, s, a, d_v, d0,
-                         Lp, G, std::min(p->sv_budget, G.budget), redo ? d_os : redo_l ? d_om : d_ov, d_ok, d_ovv,
-                         d_on);
+                         Lp, G, std::min(p->sv_budget, G.budget), (redo || redo_l) ? first : d_ov, d_ok, d_ovv, d_on,
+                         sd1);
       HIP_OK(hipGetLastError());
-      if (redo_l) {
+      if (redo_l || redo_s) {
         // (grid: the class overflows ~7 % of its sources at RMAT-22; past the grid the host takes them)
         const unsigned gl = (unsigned)std::min<size_t>(cnt_c, cnt_c / 8 + 64);
+        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_LARGE)};
         hipLaunchKernelGGL(k_sv1_list, dim3(gl), dim3(SV_LARGE.threads()), sv_lds_bytes(Lp, SV_LARGE), cs[c],
-                           g, s, a, d_v, d_om, Lp, SV_LARGE, std::min(p->sv_budget, SV_LARGE.budget), d_ov, d_ok, d_ovv,
-                           d_on);
+                           g, s, a, d_v, first, Lp, SV_LARGE, std::min(p->sv_budget, SV_LARGE.budget), d_ov, d_ok, d_ovv,
+                           d_on, sd2);
         HIP_OK(hipGetLastError());
         p->merge_launches++;
       }
       if (redo) {
+        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_MID)};
         hipLaunchKernelGGL(k_sv1_redo, dim3((unsigned)std::min<size_t>(cnt_c, 512)), dim3(SV_MID.threads()),
                            sv_lds_bytes(Lp, SV_MID), cs[c], g, s, a, d_v, d_os, Lp, SV_MID,
-                           std::min(p->sv_budget, SV_MID.budget), d_ov, d_ok, d_ovv, d_on);
+                           std::min(p->sv_budget, SV_MID.budget), d_ov, d_ok, d_ovv, d_on, sd2);
         HIP_OK(hipGetLastError());
         p->merge_launches++;
       }
@@ -1919,22 +1949,37 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
     double bytes = 0.0;
     for (size_t k = 0; k < nm; k++) bytes += sv_algo_bytes((size_t)run.pos[k]);
     kst_begin(p, 4, s1);
-    hipLaunchKernelGGL(k_svA, dim3((unsigned)nt), dim3(SV_THREADS), lds, s1, g, s, a, d_d, d_t, Lp, d_sk, d_pt);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_svB, dim3((unsigned)nt), dim3(SV_THREADS), lds, s1, g, s, a, d_d, d_t, Lp, p->sv_budget, d_sk,
-                       d_pt, d_gk, d_ga, d_gb, d_of);
-    HIP_OK(hipGetLastError());
-    hipLaunchKernelGGL(k_svF, dim3((unsigned)nm), dim3(256), svf_lds_bytes(Lp), s1, s, a, d_d, Lp, d_pt, d_gk, d_ga,
-                       d_gb, d_of, d_ov, maxdiff, p->d_stats);
-    HIP_OK(hipGetLastError());
+    // the chain, and (re-seeding on) once more for the descriptors whose first attempt overflowed:
+    // k_svS marks them and writes their seeds, every other block of the second chain leaves at once
+    const SvSeed rs{d_mk, d_cn, seed_on(SV_LARGE) ? 1 : 0, seed_budget(SV_LARGE)};
+    for (int retry = 0; retry <= rs.on; retry++) {
+      hipLaunchKernelGGL(k_svA, dim3((unsigned)nt), dim3(SV_THREADS), lds, s1, g, s, a, d_d, d_t, Lp, d_sk, d_pt, rs,
+                         d_sd, retry);
+      HIP_OK(hipGetLastError());
+      hipLaunchKernelGGL(k_svB, dim3((unsigned)nt), dim3(SV_THREADS), lds, s1, g, s, a, d_d, d_t, Lp, p->sv_budget,
+                         d_sk, d_pt, d_gk, d_ga, d_gb, d_of, rs, d_sd, retry);
+      HIP_OK(hipGetLastError());
+      hipLaunchKernelGGL(k_svF, dim3((unsigned)nm), dim3(256), svf_lds_bytes(Lp), s1, s, a, d_d, Lp, d_pt, d_gk, d_ga,
+                         d_gb, d_of, d_ov, maxdiff, p->d_stats, rs, d_sd, retry);
+      HIP_OK(hipGetLastError());
+      p->merge_launches += 3;
+      if (!retry && rs.on) {
+        hipLaunchKernelGGL(k_svS, dim3((unsigned)nm), dim3(256), 0, s1, s, a, d_d, Lp, d_pt, d_gk, d_ga, d_gb, d_sk,
+                           d_of, rs, d_sd);
+        HIP_OK(hipGetLastError());
+        p->merge_launches++;
+      }
+    }
     kst_end(p, 4, s1, bytes);
-    p->merge_launches += 3;
   }
   sub_lap(p, 6, tsub);  // sieve planning: launches
   p->sv_sources += (int64_t)nx;
   run.o_ovl = o_ov;
   run.o_os = o_os;
   run.o_om = o_om;
+  run.o_cnt = o_cn;
+  run.cls_end[0] = nm;
+  for (int c = 0; c < 3; c++) run.cls_end[1 + c] = cls_end[c];
   run.live = true;
   return PPR_OK;
 }
@@ -1952,12 +1997,15 @@ static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
     HIP_OK(hipEventRecord(p->ev_sv, p->stream_sv3));
     HIP_OK(hipStreamWaitEvent(p->stream_sv, p->ev_sv, 0));
   }
-  int32_t novf = 0, nsm = 0, nmd = 0;
+  int32_t novf = 0, nsm = 0, nmd = 0, nrs[2] = {0, 0};
+  HIP_OK(hipMemcpyAsync(nrs, p->d_sv + run.o_cnt, 8, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&novf, p->d_sv + run.o_ovl, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&nsm, p->d_sv + run.o_os, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&nmd, p->d_sv + run.o_om, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipStreamSynchronize(p->stream_sv));
   p->sv_redo_dev += nsm + nmd;
+  p->sv_reseed_n += nrs[0];
+  p->sv_reseed_ok += nrs[1];
   for (int g = 1; g < ppr_plan::NKST; g++) kst_fold(p, g);
   if (!novf) return PPR_OK;
   std::vector<int32_t> od(novf);
@@ -2076,12 +2124,28 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   lap(3, tl);  // range / partition engines (their syncs included)
   std::vector<int32_t>& back = p->xhs.back;
   back.clear();
-  const int64_t dev0 = p->sv_redo_dev;
+  const int64_t dev0 = p->sv_redo_dev, rs0 = p->sv_reseed_n, rk0 = p->sv_reseed_ok;
   { int r = sieve_collect(p, run, back); if (r) return r; }
   lap(4, tl);  // waiting for the sieve
-  if (getenv("PPR_SV_LOG"))
-    fprintf(stderr, "ppr_sv_log it %d sieved %zu range %zu dev_redo %lld handed_back %zu\n", a.iter, ssrc.size(),
-            src.size(), (long long)(p->sv_redo_dev - dev0), back.size());
+  if (getenv("PPR_SV_LOG")) {
+    // hand-backs by class (sources, and the candidates they carry): the large, mid and small one-slice
+    // classes (the small class after its device redo) and the multi-slice sources
+    // (a source's class from its descriptor index: run.pos maps descriptors to sources, inverted here)
+    long long hn[4] = {0, 0, 0, 0}, hc[4] = {0, 0, 0, 0}, sc = 0;
+    std::vector<int32_t> desc_of(ssrc.size(), 0);
+    for (size_t d = 0; d < run.pos.size(); d++) desc_of[(size_t)run.pos[d]] = (int32_t)d;
+    for (size_t k = 0; k < back.size(); k++) {
+      int c = 0;
+      while (c < 3 && (size_t)desc_of[(size_t)back[k]] >= run.cls_end[c]) c++;
+      hn[c]++;
+      hc[c] += h[nh + (size_t)sidx[(size_t)back[k]]];
+    }
+    for (int32_t c : scand) sc += c;
+    fprintf(stderr, "ppr_sv_log it %d sieved %zu range %zu dev_redo %lld handed_back %zu sieved_cand %lld "
+            "hb_large %lld %lld hb_mid %lld %lld hb_small %lld %lld hb_multi %lld %lld reseed %lld reseed_ok %lld\n",
+            a.iter, ssrc.size(), src.size(), (long long)(p->sv_redo_dev - dev0), back.size(), sc, hn[1], hc[1], hn[2],
+            hc[2], hn[3], hc[3], hn[0], hc[0], (long long)(p->sv_reseed_n - rs0), (long long)(p->sv_reseed_ok - rk0));
+  }
   if (back.empty()) return PPR_OK;
   // handed back: the range / partition engines, with the usual estimate
   src.clear(); cand.clear(); deg.clear(); dest.clear();

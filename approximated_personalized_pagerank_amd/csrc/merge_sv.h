@@ -17,9 +17,18 @@
 //           and cannot be in the top-L (nor tied at its cut).
 //   select  top-L of PT u XT by (value desc, tie hash desc) -- the same set and the same order as
 //           the exact sum over all keys (merge_xs.h), so the row, norm1 and maxDiff are bit-identical.
-// A source whose passing keys overflow XT is handed back to the range / partition engines of
-// merge_xs.h (correct either way, slower). Sources whose current row is not full (no L keys to
-// bound with) never enter the sieve.
+// The bound only needs L distinct keys with exact totals; the previous row is one choice, and in
+// the first iterations a poor one (RMAT-22 iteration 2: a bound of 2.3e-05 against a true theta of
+// 6.7e-05, 18-21 K passing keys for a table of 2457). So a source whose passing keys overflow XT is
+// RE-SEEDED and retried once on the device (PPR_SV_RESEED, default on): the overflowed attempt takes
+// the top-L by value of PT u the keys resident in XT as its seeds -- L distinct keys (sv_insert
+// skips PT keys) whose L-th largest value is >= theta, PT's values being exact and XT's lower
+// bounds (past the budget no key enters XT, the resident ones go on accumulating) -- and the second
+// attempt builds PT from the seeds: the same algorithm with a bound theta' >= theta, the same
+// bit-exact row. Seeds are written only when the table's budget is at least Lp (a smaller table
+// cannot improve on PT). A second overflow, or a first one with re-seeding off, hands the source
+// back to the range / partition engines of merge_xs.h (correct either way, slower). Sources whose
+// current row is not full (no L keys to bound with) never enter the sieve.
 //
 // Exact accumulators: X = sum floor(p * 2^93) (oracle/grank_oracle.c "exact") held as two u64
 // words that are only ever added to -- A = sum of the low 32 bits of each X_i, B = sum of X_i >> 32
@@ -32,6 +41,10 @@
 //   k_svB   pass 2 of one slice: bound and sieve from the global copies, XT flushed into the
 //           source's global table
 //   k_svF   one workgroup per multi-slice source: top-L of PT u global table, row
+// Retries (same stream, no host round trip): k_sv1_redo (small class -> mid geometry) and k_sv1_list
+// (mid -> large with PPR_SV_REDO_LARGE=1; large -> large, re-seeded) take a class's first overflows;
+// k_svS seeds the multi-slice sources whose first chain overflowed and the chain runs once more for
+// them (every other block of the second chain leaves before it touches LDS).
 #pragma once
 #include "merge_xs.h"
 
@@ -329,18 +342,17 @@ __device__ __forceinline__ void sv_lap(const IterArgs& a, int slot, long long& t
   t = now;
 }
 
-// the current row of v (L distinct keys) into PT with zeroed sums (dummies included); misc cleared
-__device__ __forceinline__ void sv_build_pt(const SvLds& x, const DevSlab& s, const IterArgs& a, int v, int Lp) {
+// PT from a list of n <= L distinct keys (keyat(i), tags below 2^31) with zeroed sums (dummies
+// included); misc cleared. pos[slot] = the key's index in the list.
+template <class KeyAt>
+__device__ __forceinline__ void sv_build_pt_keys(const SvLds& x, int n, KeyAt keyat) {
   const SvPt& t = x.pt;
   for (int i = threadIdx.x; i < t.T; i += blockDim.x) t.keys[i] = 0u;
   for (int i = threadIdx.x; i < 2 * (t.T + 64); i += blockDim.x) t.ab[i] = 0ull;
   if (threadIdx.x < 64) x.misc[threadIdx.x] = 0;
   __syncthreads();
-  const int cur = (a.active == 1) ? a.sB : a.sA;
-  const int64_t r = s.row(cur, v);
-  const int len = s.len[s.lrow(cur, v)];
-  for (int i = threadIdx.x; i < len; i += blockDim.x) {
-    const int key = s.key(s.ids[r + i]);
+  for (int i = threadIdx.x; i < n; i += blockDim.x) {
+    const int key = keyat(i);
     const uint32_t tag = (uint32_t)key + 1u;
     const uint32_t home = svpt_home(t, sv_hash(key).h0);
     uint32_t g4 = home;
@@ -354,6 +366,15 @@ __device__ __forceinline__ void sv_build_pt(const SvLds& x, const DevSlab& s, co
       g4 = (g4 + 4u) & (uint32_t)(t.T - 1);
     }
   }
+}
+// PT of source v: the L keys of its current row, or (a seeded attempt, `seeds` != nullptr) the L
+// seed keys an overflowed first attempt wrote
+__device__ __forceinline__ void sv_build_pt(const SvLds& x, const DevSlab& s, const IterArgs& a, int v, int Lp,
+                                            const int32_t* seeds = nullptr) {
+  const int cur = (a.active == 1) ? a.sB : a.sA;
+  const int64_t r = s.row(cur, v);
+  const int len = s.len[s.lrow(cur, v)];
+  sv_build_pt_keys(x, len, [&](int i) { return seeds ? (int)seeds[i] : s.key(s.ids[r + i]); });
 }
 
 // The wave's share of a slice: contiguous successors [c0, c1) taken row by row. Row metadata comes
@@ -531,13 +552,19 @@ __device__ __forceinline__ void sv_pass1(const DevGraph& g, const DevSlab& s, co
 #endif
 // insert `n` (<= 64) candidates (key, t = p * 2^61) of the wave into XT: PT keys skipped
 __device__ __forceinline__ void sv_insert(const SvLds& x, const X2Table& xt, const IterArgs& a, bool live, int key,
-                                          double t, int budget) {
+                                          double t, int budget, bool keep) {
   const int lane = lane_id();
   const bool w = live && svpt_slot(x.pt, key, sv_hash(key).h0, live) < 0;
   if (!__ballot(w)) return;
   if (a.diag && lane == 0) diag_add(a.diag, 148, 1ull);
   if (__hip_atomic_load(&x.misc[SVM_FILL], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) > budget) {
     if (lane == 0) x.misc[SVM_OVF] = 1;
+    // (`keep`: the attempt will seed a retry from the resident keys -- they go on accumulating, no
+    // new key enters, so their totals are whole and the seeds' bound is as high as it can be)
+    if (keep) {
+      const int hs = w ? x2_find(xt, key) : -1;
+      if (hs >= 0) sv_split_add_t(xt.a, xt.b, hs, t);
+    }
     return;
   }
   bool ins = false;
@@ -550,7 +577,8 @@ __device__ __forceinline__ void sv_insert(const SvLds& x, const X2Table& xt, con
   if (a.diag && lane == 0) diag_add(a.diag, 138, (unsigned long long)__popcll(__ballot(w)));
 }
 __device__ __forceinline__ void sv_pass2(const DevGraph& g, const DevSlab& s, const IterArgs& a, const SvLds& x,
-                                         const X2Table& xt, int64_t b0, int64_t b1, double factor, int budget) {
+                                         const X2Table& xt, int64_t b0, int64_t b1, double factor, int budget,
+                                         bool keep = false) {
   int64_t c0, c1;
   sv_chunk(b0, b1, c0, c1);
   const uint32_t* bm32 = reinterpret_cast<const uint32_t*>(x.bm);
@@ -581,7 +609,7 @@ __device__ __forceinline__ void sv_pass2(const DevGraph& g, const DevSlab& s, co
   };
   auto complete = [&]() {
     if (pn) {
-      sv_insert(x, xt, a, lane < pn, pk, SV_P2_SCORES ? pt : pt * f61, budget);
+      sv_insert(x, xt, a, lane < pn, pk, SV_P2_SCORES ? pt : pt * f61, budget, keep);
       pn = 0;
     }
   };
@@ -632,7 +660,7 @@ __device__ __forceinline__ void sv_pass2(const DevGraph& g, const DevSlab& s, co
     for (int k = 0; k < NG; k++) {
       if (!__ballot(want[k])) continue;
       const double sc = SV_P2_SCORES ? bt.sv[k] : (want[k] ? s.sc[bt.base[k >> 1] + (k & 1) * WAVE + lane] : 0.0);
-      sv_insert(x, xt, a, want[k], bt.key[k], sc * f61, budget);
+      sv_insert(x, xt, a, want[k], bt.key[k], sc * f61, budget, keep);
     }
   });
   complete();
@@ -713,14 +741,32 @@ __device__ __forceinline__ void sv_clear_region(const SvLds& x, size_t bytes) {
 __host__ __device__ constexpr int sv_ostride(int Lp) { return PPR_SV_OSTRIDE_X * Lp; }
 
 // ---------------------------------------------------------------------------------------------
+// Re-seeding (header comment): a first attempt that overflows writes L seed keys and is retried on
+// the device with PT built from them. One-slice sources keep the seeds in their own (unused) entries
+// of the k_sv1 -> k_svfin key list and mark them with out_n[d] = SV_SEEDED.
+constexpr int32_t SV_SEEDED = -1;
+struct SvSeed {
+  int32_t* retry;   // one-slice: the list a seeded source is appended to ([0] count, [1..] descriptors);
+                    // nullptr: no retry runs behind this launch. Multi-slice: the per-descriptor marks.
+  int32_t* cnt;     // [0] seeded attempts, [1] those that completed
+  int32_t on;       // seeds are written and used (PPR_SV_RESEED, and a table budget of at least Lp)
+  int32_t budget;   // table budget of a seeded attempt (PPR_SV_RESEED_BUDGET; 0: it always overflows)
+};
+
 // one source (descriptor d) of a one-slice class, the whole workgroup; a source that overflows
-// (or has no full row) goes to `ovl` and writes nothing
+// (or has no full row) goes to `ovl` and writes nothing -- or, a first overflow with a retry behind
+// it, writes its seeds and goes to `sd.retry`
 __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevSlab s, IterArgs a, const int32_t* vid,
                                            int d, int Lp, SvGeom G, int budget, int32_t* ovl, int32_t* out_k,
-                                           double* out_v, int32_t* out_n) {
+                                           double* out_v, int32_t* out_n, SvSeed sd) {
   const SvLds x = sv_carve(smem, Lp, G);
   const int v = vid[d];
   const int L = s.L;
+  int32_t* ok = out_k + (int64_t)d * sv_ostride(Lp);
+  double* ov = out_v + (int64_t)d * sv_ostride(Lp);
+  // a seeded attempt: PT from the seeds the first attempt left in `ok` (workgroup-uniform)
+  const bool seeded = sd.on && out_n[d] == SV_SEEDED;
+  if (seeded) budget = sd.budget;
   // (the host sends only sources with a full current row: L keys to bound with)
   if (s.len[s.lrow((a.active == 1) ? a.sB : a.sA, v)] != L) {
     if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
@@ -731,15 +777,18 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   const int dg = 256 + 8 * (G.wlog == 13 ? 0 : G.wlog == 12 ? 1 : 2);
   uint32_t* sk = reinterpret_cast<uint32_t*>(x.region);
   sv_clear_region(x, G.sketch_bytes());
-  sv_build_pt(x, s, a, v, Lp);
+  sv_build_pt(x, s, a, v, Lp, seeded ? ok : nullptr);
   __syncthreads();
   if (threadIdx.x == 0) {
     *reinterpret_cast<unsigned long long*>(&x.misc[SVM_THETA]) = ~0ull;
     sv_seed1(x, v, 1.0 - a.damping, sk);
+    if (seeded) atomicAdd(&sd.cnt[0], 1);
   }
   sv_lap(a, dg + 0, tph);
   const int64_t b = g.rp[v], e = g.rp[v + 1];
   const double factor = merge_factor(a, e - b);
+  // a first attempt that may seed a retry (should it overflow)
+  const bool reseed = !seeded && sd.on && sd.retry != nullptr;
   sv_pass1(g, s, a, x, b, e, factor, sk);
   __syncthreads();
   sv_lap(a, dg + 1, tph);
@@ -759,21 +808,27 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   // nothing (exact skip)
   if (sv_rows_all(x) || (a.whatif & WI_SV_NO_P2SKIP)) {
     if (threadIdx.x == 0) sv_seed2(x, xt, v, 1.0 - a.damping);
-    sv_pass2(g, s, a, x, xt, b, e, factor, budget);
+    sv_pass2(g, s, a, x, xt, b, e, factor, budget, reseed);
     __syncthreads();
   } else if (a.diag && threadIdx.x == 0) {
     diag_add(a.diag, 145, 1ull);
   }
   sv_lap(a, dg + 3, tph);
   if (a.diag && threadIdx.x == 0) { diag_add(a.diag, dg + 5, 1ull); diag_add(a.diag, dg + 6, (unsigned long long)(e - b)); }
-  if (x.misc[SVM_OVF] || x.misc[SVM_FILL] > budget + G.waves * WAVE) {
-    if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+  const bool ovf = x.misc[SVM_OVF] || x.misc[SVM_FILL] > budget + G.waves * WAVE || (seeded && sd.budget <= 0);
+  if (ovf && !reseed) {
+    if (threadIdx.x == 0) {
+      ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+      if (seeded) out_n[d] = 0;  // (k_svfin: handed back)
+    }
     if (a.diag && threadIdx.x == 0) { diag_add(a.diag, 137, 1ull); diag_add(a.diag, dg + 7, 1ull); }
     return;
   }
   // dense (value, key) list of PT u {XT keys >= theta}: the table's slot values into registers
   // (SV_XS per thread), then written over the front of the region after every slot was read; the
-  // PT entries (outside the region) after them
+  // PT entries (outside the region) after them. An overflowed first attempt that seeds its retry
+  // (`ovf`) lists every resident XT key instead: the top-L of that list are the seeds (L distinct
+  // keys whose L-th largest total is at least theta -- PT's values are exact, XT's lower bounds).
   double xv[SV_XS];
   int xk[SV_XS];
   int c = 0;
@@ -782,7 +837,7 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
     const int i = (int)threadIdx.x + j * (int)blockDim.x;
     const uint32_t kt = xt.keys[i];
     const double val = kt ? x2_value(xt.a[i], xt.b[i]) : 0.0;
-    xk[j] = (kt && val >= theta) ? (int)kt - 1 : -1;
+    xk[j] = (kt && (ovf || val >= theta)) ? (int)kt - 1 : -1;
     xv[j] = val;
     c += xk[j] >= 0;
   }
@@ -809,7 +864,7 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   }
   __syncthreads();
   const int U = x.misc[SVM_U];
-  if (a.diag && threadIdx.x == 0) {
+  if (a.diag && threadIdx.x == 0 && !ovf) {
     diag_add(a.diag, 135, 1ull);
     diag_add(a.diag, 136, (unsigned long long)x.misc[SVM_FILL]);
     diag_add(a.diag, 139, (unsigned long long)(U - L));
@@ -820,7 +875,8 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   const uint32_t ts = tie_salt(v);
   SelCrit sc;
   sc.tie = false; sc.pa = 0; sc.ma = 0; sc.pb = 0; sc.mb = 0;
-  const bool cut = U > sv_ostride(Lp);  // (else k_svfin selects: every kept entry goes to the list)
+  // (else k_svfin selects: every kept entry goes to the list; seeds: exactly the top-L)
+  const bool cut = U > (ovf ? L : sv_ostride(Lp));
   if (cut) {
     WgLds w = WgLds{};
     w.hist = x.hist;
@@ -829,8 +885,6 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   }
   if (threadIdx.x == 0) x.misc[SVM_PT] = 0;
   __syncthreads();
-  int32_t* ok = out_k + (int64_t)d * sv_ostride(Lp);
-  double* ov = out_v + (int64_t)d * sv_ostride(Lp);
   for (int i0 = 0; i0 < U; i0 += blockDim.x) {
     const int i = i0 + threadIdx.x;
     const bool sel = i < U && (!cut || sel_test(sc, dbits(dv[i]), tie_w(dk[i], ts)));
@@ -840,20 +894,29 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
     b0 = __shfl(b0, 0);
     if (sel) {
       const int pos = b0 + __popcll(m & lanemask_lt());
-      ok[pos] = dk[i];
-      ov[pos] = dv[i];
+      // (the seeds are L keys: a tie the tie hash does not split selects more, any L of them do)
+      if (!ovf || pos < L) { ok[pos] = dk[i]; ov[pos] = dv[i]; }
     }
   }
   __syncthreads();
-  if (threadIdx.x == 0) out_n[d] = x.misc[SVM_PT];
+  if (threadIdx.x == 0) {
+    if (ovf) {  // seeds written: the source's retry finds them by the mark
+      out_n[d] = SV_SEEDED;
+      sd.retry[1 + atomicAdd(&sd.retry[0], 1)] = d;
+      if (a.diag) { diag_add(a.diag, 137, 1ull); diag_add(a.diag, dg + 7, 1ull); }
+    } else {
+      out_n[d] = x.misc[SVM_PT];
+      if (seeded) atomicAdd(&sd.cnt[1], 1);
+    }
+  }
   if (threadIdx.x == 0) sv_lap(a, dg + 4, tph);
 }
 
 __global__ void __launch_bounds__(SV_THREADS) k_sv1(DevGraph g, DevSlab s, IterArgs a, const int32_t* vid, int d0,
                                                     int Lp, SvGeom G, int budget, int32_t* ovl, int32_t* out_k,
-                                                    double* out_v, int32_t* out_n) {
+                                                    double* out_v, int32_t* out_n, SvSeed sd) {
   extern __shared__ __align__(16) unsigned char smem[];
-  sv1_source(smem, g, s, a, vid, d0 + (int)blockIdx.x, Lp, G, budget, ovl, out_k, out_v, out_n);
+  sv1_source(smem, g, s, a, vid, d0 + (int)blockIdx.x, Lp, G, budget, ovl, out_k, out_v, out_n, sd);
 }
 
 // the sources a smaller class handed back (`list`: [0] count, [1..] descriptors), again with a
@@ -864,12 +927,12 @@ static_assert(SV_MID.waves == 8, "k_sv1_redo launch bounds: the mid geometry");
 __global__ void __launch_bounds__(8 * WAVE) k_sv1_redo(DevGraph g, DevSlab s, IterArgs a, const int32_t* vid,
                                                          const int32_t* list, int Lp, SvGeom G, int budget,
                                                          int32_t* ovl, int32_t* out_k, double* out_v,
-                                                         int32_t* out_n) {
+                                                         int32_t* out_n, SvSeed sd) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = list[0];
   for (int k = (int)blockIdx.x; k < n; k += (int)gridDim.x) {
     __syncthreads();  // the previous source's LDS reads are done
-    sv1_source(smem, g, s, a, vid, list[1 + k], Lp, G, budget, ovl, out_k, out_v, out_n);
+    sv1_source(smem, g, s, a, vid, list[1 + k], Lp, G, budget, ovl, out_k, out_v, out_n, sd);
   }
 }
 
@@ -883,13 +946,13 @@ __global__ void __launch_bounds__(8 * WAVE) k_sv1_redo(DevGraph g, DevSlab s, It
 __global__ void __launch_bounds__(SV_THREADS) k_sv1_list(DevGraph g, DevSlab s, IterArgs a, const int32_t* vid,
                                                          const int32_t* list, int Lp, SvGeom G, int budget,
                                                          int32_t* ovl, int32_t* out_k, double* out_v,
-                                                         int32_t* out_n) {
+                                                         int32_t* out_n, SvSeed sd) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int n = list[0];
   if (blockIdx.x == 0)  // more overflows than blocks: the rest go to the host hand-back at once
     for (int k = (int)gridDim.x + (int)threadIdx.x; k < n; k += (int)blockDim.x) ovl[1 + atomicAdd(&ovl[0], 1)] = list[1 + k];
   if ((int)blockIdx.x >= n) return;
-  sv1_source(smem, g, s, a, vid, list[1 + blockIdx.x], Lp, G, budget, ovl, out_k, out_v, out_n);
+  sv1_source(smem, g, s, a, vid, list[1 + blockIdx.x], Lp, G, budget, ovl, out_k, out_v, out_n, sd);
 }
 
 // the row of a one-slice source from its entries (k_sv1; more than L: the top-L first): one wave
@@ -902,7 +965,9 @@ __global__ void __launch_bounds__(64) k_svfin(DevSlab s, IterArgs a, const int32
   extern __shared__ __align__(16) unsigned char smem[];
   const int d = d0 + (int)blockIdx.x;
   const int n = in_n[d];
-  if (n <= 0) return;  // handed back (a written source has L >= 1 entries)
+  // handed back (a written source has L >= 1 entries): 0, or SV_SEEDED (< 0) where a seeded source
+  // never got its retry (k_sv1_list: first overflows past the retry grid go to the host at once)
+  if (n <= 0) return;
   const int v = vid[d];
   uint64_t* rv = reinterpret_cast<uint64_t*>(smem);
   int* rk = reinterpret_cast<int*>(smem + (size_t)Lp * 8);
@@ -925,18 +990,25 @@ __device__ __forceinline__ void sv_slice(int64_t b, int64_t e, int k, int S, int
 
 __global__ void __launch_bounds__(SV_THREADS) k_svA(DevGraph g, DevSlab s, IterArgs a, const SvDesc* desc,
                                                     const SvTask* tasks, int Lp, uint32_t* gsk,
-                                                    unsigned long long* gpt) {
+                                                    unsigned long long* gpt, SvSeed rs, const int32_t* seeds,
+                                                    int retry) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr SvGeom G = SV_LARGE;
-  const SvLds x = sv_carve(smem, Lp, G);
   const SvTask tk = tasks[blockIdx.x];
+  // the retry chain (k_svS marked the descriptors whose first attempt overflowed and wrote their
+  // seeds): every other descriptor's slices leave at once
+  if (retry && !rs.retry[tk.d]) return;
+  const SvLds x = sv_carve(smem, Lp, G);
   const SvDesc sd = desc[tk.d];
   const int v = sd.v;
   uint32_t* sk = reinterpret_cast<uint32_t*>(x.region);
   sv_clear_region(x, G.sketch_bytes());
-  sv_build_pt(x, s, a, v, Lp);
+  sv_build_pt(x, s, a, v, Lp, retry ? seeds + (int64_t)tk.d * Lp : nullptr);
   __syncthreads();
-  if (tk.k == 0 && threadIdx.x == 0) sv_seed1(x, v, 1.0 - a.damping, sk);
+  if (tk.k == 0 && threadIdx.x == 0) {
+    sv_seed1(x, v, 1.0 - a.damping, sk);
+    if (retry) atomicAdd(&rs.cnt[0], 1);
+  }
   int64_t b0, b1;
   sv_slice(g.rp[v], g.rp[v + 1], tk.k, sd.S, b0, b1);
   sv_pass1(g, s, a, x, b0, b1, sd.factor, sk);
@@ -975,15 +1047,24 @@ __device__ __forceinline__ int64_t sv_gslot(uint32_t* keys, int64_t T, int key) 
 __global__ void __launch_bounds__(SV_THREADS) k_svB(DevGraph g, DevSlab s, IterArgs a, const SvDesc* desc,
                                                     const SvTask* tasks, int Lp, int budget, const uint32_t* gsk,
                                                     const unsigned long long* gpt, uint32_t* gkeys,
-                                                    unsigned long long* ga, unsigned long long* gb, int32_t* oflag) {
+                                                    unsigned long long* ga, unsigned long long* gb, int32_t* oflag,
+                                                    SvSeed rs, const int32_t* seeds, int retry) {
   extern __shared__ __align__(16) unsigned char smem[];
   constexpr SvGeom G = SV_LARGE;
-  const SvLds x = sv_carve(smem, Lp, G);
   const SvTask tk = tasks[blockIdx.x];
+  if (retry && !rs.retry[tk.d]) return;
+  if (retry) budget = rs.budget;
+  if (retry && rs.budget <= 0) {  // (tests: the seeded attempt overflows)
+    if (threadIdx.x == 0) oflag[tk.d] = 1;
+    return;
+  }
+  // a first attempt that overflows still flushes its resident keys: k_svF picks the seeds from them
+  const bool keep = !retry && rs.on;
+  const SvLds x = sv_carve(smem, Lp, G);
   const SvDesc sd = desc[tk.d];
   const int v = sd.v;
   const int L = s.L;
-  sv_build_pt(x, s, a, v, Lp);
+  sv_build_pt(x, s, a, v, Lp, retry ? seeds + (int64_t)tk.d * Lp : nullptr);
   __syncthreads();
   if (threadIdx.x == 0) *reinterpret_cast<unsigned long long*>(&x.misc[SVM_THETA]) = ~0ull;
   __syncthreads();
@@ -998,13 +1079,12 @@ __global__ void __launch_bounds__(SV_THREADS) k_svB(DevGraph g, DevSlab s, IterA
   if (tk.k == 0 && threadIdx.x == 0) sv_seed2(x, xt, v, 1.0 - a.damping);
   int64_t b0, b1;
   sv_slice(g.rp[v], g.rp[v + 1], tk.k, sd.S, b0, b1);
-  sv_pass2(g, s, a, x, xt, b0, b1, sd.factor, budget);
+  sv_pass2(g, s, a, x, xt, b0, b1, sd.factor, budget, keep);
   __syncthreads();
   if (x.misc[SVM_OVF] || x.misc[SVM_FILL] > budget + G.waves * WAVE) {
     if (threadIdx.x == 0) oflag[tk.d] = 1;
-    return;
-  }
-  if (a.diag && threadIdx.x == 0) diag_add(a.diag, 136, (unsigned long long)x.misc[SVM_FILL]);
+    if (!keep) return;
+  } else if (a.diag && threadIdx.x == 0) diag_add(a.diag, 136, (unsigned long long)x.misc[SVM_FILL]);
   uint32_t* gk = gkeys + sd.gxt;
   unsigned long long* gA = ga + sd.gxt;
   unsigned long long* gB = gb + sd.gxt;
@@ -1021,6 +1101,67 @@ __global__ void __launch_bounds__(SV_THREADS) k_svB(DevGraph g, DevSlab s, IterA
   if (full) oflag[tk.d] = 1;
 }
 
+// a multi-slice source whose first attempt overflowed is seeded and retried (k_svS, then the chain
+// again) rather than handed back: re-seeding on, a full row, a table the select can index
+__device__ __forceinline__ bool sv_seeds_multi(bool ovf, bool full, int retry, const SvSeed& rs, const SvDesc& sd) {
+  return ovf && full && !retry && rs.on && sd.tg <= (1 << 30);
+}
+
+// k_svS, between the first chain and the retry chain, one workgroup per multi-slice source: a source
+// whose first attempt overflowed gets its seeds -- the top-L by value of the L PT totals (exact) and
+// the global table's entries (lower bounds: every slice flushed its resident keys), read in place --
+// its sums, sketch and table zeroed, and its mark for the retry chain. (A kernel of its own: inside
+// k_svF the select's state cost every k_svF block a wave of occupancy.)
+__global__ void __launch_bounds__(256) k_svS(DevSlab s, IterArgs a, const SvDesc* desc, int Lp,
+                                             unsigned long long* gpt, uint32_t* gkeys, unsigned long long* ga,
+                                             unsigned long long* gb, uint32_t* gsk, int32_t* oflag, SvSeed rs,
+                                             int32_t* seeds) {
+  __shared__ uint32_t hist[256];
+  __shared__ int misc[64];
+  const int d = blockIdx.x;
+  if (!oflag[d]) return;
+  const SvDesc sd = desc[d];
+  const int v = sd.v;
+  const int L = s.L;
+  const int cur = (a.active == 1) ? a.sB : a.sA;
+  if (!sv_seeds_multi(true, s.len[s.lrow(cur, v)] == L, 0, rs, sd)) return;  // (k_svF handed it back)
+  const int64_t r = s.row(cur, v);
+  unsigned long long* gp = gpt + sd.gpt;
+  int32_t* sk = seeds + (int64_t)d * Lp;
+  uint32_t* gk = gkeys + sd.gxt;
+  unsigned long long* gA = ga + sd.gxt;
+  unsigned long long* gB = gb + sd.gxt;
+  const int n = L + sd.tg;
+  auto occ = [&](int i) { return i < L || gk[i - L] != 0u; };
+  auto keyat = [&](int i) { return i < L ? s.key(s.ids[r + i]) : (int)gk[i - L] - 1; };
+  auto valat = [&](int i) {
+    return i < L ? x2_value(gp[2 * i], gp[2 * i + 1]) : x2_value(gA[i - L], gB[i - L]);
+  };
+  const uint32_t ts = tie_salt(v);
+  WgLds w = WgLds{};
+  w.hist = hist;
+  w.misc = misc;
+  const SelCrit sc = wg_select_top(w, n, L, keyat, valat, occ, ts);
+  if (threadIdx.x == 0) misc[SVM_PT] = 0;
+  __syncthreads();
+  for (int i0 = 0; i0 < n; i0 += blockDim.x) {
+    const int i = i0 + (int)threadIdx.x;
+    const bool sel = i < n && occ(i) && sel_test(sc, dbits(valat(i)), tie_w(keyat(i), ts));
+    const uint64_t m = __ballot(sel);
+    int b0 = 0;
+    if (m && lane_id() == 0) b0 = atomicAdd(&misc[SVM_PT], __popcll(m));
+    b0 = __shfl(b0, 0);
+    const int pos = b0 + __popcll(m & lanemask_lt());
+    if (sel && pos < L) sk[pos] = keyat(i);  // (a tie the tie hash does not split: any L of them)
+  }
+  __syncthreads();  // every entry read: the descriptor's sums, sketch and table start again from zero
+  for (int i = threadIdx.x; i < 2 * Lp; i += blockDim.x) gp[i] = 0ull;
+  uint32_t* gs = gsk + sd.gsk;
+  for (int i = threadIdx.x; i < SV_R * (1 << SV_LARGE.wlog); i += blockDim.x) gs[i] = 0u;
+  for (int i = threadIdx.x; i < sd.tg; i += blockDim.x) { gk[i] = 0u; gA[i] = 0ull; gB[i] = 0ull; }
+  if (threadIdx.x == 0) { rs.retry[d] = 1; oflag[d] = 0; }
+}
+
 // k_svF LDS: dense values f64[SVF_CAP + Lp] | keys i32[SVF_CAP + Lp] | misc | finish_source scratch
 __host__ __device__ constexpr size_t svf_lds_bytes(int Lp) {
   return (size_t)(SVF_CAP + Lp) * 12 + 256 + 1024 + (size_t)Lp * 32;
@@ -1029,9 +1170,10 @@ __global__ void __launch_bounds__(256) k_svF(DevSlab s, IterArgs a, const SvDesc
                                              const unsigned long long* gpt, const uint32_t* gkeys,
                                              const unsigned long long* ga, const unsigned long long* gb,
                                              const int32_t* oflag, int32_t* ovl, unsigned long long* maxdiff,
-                                             unsigned long long* stats) {
+                                             unsigned long long* stats, SvSeed rs, const int32_t* seeds, int retry) {
   extern __shared__ __align__(16) unsigned char smem[];
   const int d = blockIdx.x;
+  if (retry && !rs.retry[d]) return;
   const SvDesc sd = desc[d];
   const int v = sd.v;
   const int L = s.L;
@@ -1046,22 +1188,27 @@ __global__ void __launch_bounds__(256) k_svF(DevSlab s, IterArgs a, const SvDesc
   int* hk = reinterpret_cast<int*>(p); p += (size_t)Lp * 8;
   int* hv = reinterpret_cast<int*>(p); p += (size_t)Lp * 8;
   int* mf = reinterpret_cast<int*>(p);
-  if (oflag[d] || s.len[s.lrow((a.active == 1) ? a.sB : a.sA, v)] != L) {
-    if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+  const bool full = s.len[s.lrow((a.active == 1) ? a.sB : a.sA, v)] == L;
+  if (oflag[d] || !full) {
+    // (a first overflow that k_svS will seed for the retry chain stays off the hand-back list)
+    if (!sv_seeds_multi(oflag[d] != 0, full, retry, rs, sd)) {
+      if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+    }
     return;
   }
-  if (threadIdx.x < 64) misc[threadIdx.x] = 0;
-  if (threadIdx.x == 0) *reinterpret_cast<unsigned long long*>(&misc[SVM_THETA]) = ~0ull;
-  __syncthreads();
   const unsigned long long* gp = gpt + sd.gpt;
   const int cur = (a.active == 1) ? a.sB : a.sA;
   const int64_t r = s.row(cur, v);
+  const int32_t* sk = seeds + (int64_t)d * Lp;
+  if (threadIdx.x < 64) misc[threadIdx.x] = 0;
+  if (threadIdx.x == 0) *reinterpret_cast<unsigned long long*>(&misc[SVM_THETA]) = ~0ull;
+  __syncthreads();
   // the L prev keys with their exact totals (all >= theta), then the table's keys >= theta
   unsigned long long mn = ~0ull;
   for (int i = threadIdx.x; i < L; i += blockDim.x) {
     const double val = x2_value(gp[2 * i], gp[2 * i + 1]);
     dv[i] = val;
-    dk[i] = s.key(s.ids[r + i]);
+    dk[i] = retry ? (int)sk[i] : s.key(s.ids[r + i]);
     const unsigned long long bb = dbits(val);
     mn = bb < mn ? bb : mn;
   }
@@ -1099,6 +1246,7 @@ __global__ void __launch_bounds__(256) k_svF(DevSlab s, IterArgs a, const SvDesc
     diag_add(a.diag, 149, 1ull);
     diag_add(a.diag, 139, (unsigned long long)(U - L));
   }
+  if (retry && threadIdx.x == 0) atomicAdd(&rs.cnt[1], 1);
   if (threadIdx.x < WAVE)
     finish_source(v, U, [&](int i) { return dk[i]; }, [&](int i) { return dv[i]; }, s, a, hist, rv, rk, Lp, hk, hv,
                   mf, maxdiff, stats);

@@ -264,6 +264,9 @@ struct ppr_plan {
                                       // off by default: at RMAT-22 the mid class now overflows ~1 source per job,
                                       // and the redo grid's 113-KB workgroups still pass through the CUs)
   int sv_budget = 2457;               // PPR_SV_BUDGET (tests): passing keys a table takes (<= SV_XT_BUDGET)
+  bool sv_reseed = true;              // PPR_SV_RESEED=0: an overflowed source is handed on as before, no seeded retry
+  int sv_reseed_budget = -1;          // PPR_SV_RESEED_BUDGET (tests): table budget of the seeded attempts only
+                                      // (0: every seeded attempt overflows); -1: the attempt's usual budget
   int64_t sv_small = 32768, sv_mid = 65536;  // PPR_SV_SMALL / PPR_SV_MID: one-slice size classes by candidates
                                       // (same-box sweep of SV_SMALL 16 K / 32 K / 48 K / 64 K: 1632 / 1589-1594 /
                                       // 1593 / 1664 ms per job; SV_MID 32 K / 131 K: +-0)
@@ -276,6 +279,7 @@ struct ppr_plan {
   size_t h_sv_bytes = 0;
   int64_t sv_sources = 0, sv_redo = 0;  // sieved sources, handed back after an overflow (PPR_TIMING)
   int64_t sv_redo_dev = 0;            // small / mid-class overflows redone on the device (mid / large geometry)
+  int64_t sv_reseed_n = 0, sv_reseed_ok = 0;  // seeded attempts (every class, multi-slice too), those that completed
   double xh_s[8] = {};                // run_xhubs host sections, s (PPR_TIMING at destroy)
   // preference-set queries (query.hip): grow-only scratch of one chunk, kept across calls
   unsigned char* d_q = nullptr;       // query arrays, planner verdicts, tier lists, outputs
@@ -343,8 +347,9 @@ inline void plan_free(ppr_plan* p) {
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (getenv("PPR_TIMING") && p->sv_sources)
-    fprintf(stderr, "ppr_timing sieve_sources %lld sieve_redo %lld sieve_redo_dev %lld\n", (long long)p->sv_sources,
-            (long long)p->sv_redo, (long long)p->sv_redo_dev);
+    fprintf(stderr, "ppr_timing sieve_sources %lld sieve_redo %lld sieve_redo_dev %lld sieve_reseed %lld "
+            "sieve_reseed_ok %lld\n", (long long)p->sv_sources, (long long)p->sv_redo, (long long)p->sv_redo_dev,
+            (long long)p->sv_reseed_n, (long long)p->sv_reseed_ok);
   if (getenv("PPR_TIMING") && p->sv_sources)
     fprintf(stderr, "ppr_timing xhubs_host_s gather %.4f classify %.4f sieve_launch %.4f engines %.4f sieve_wait %.4f "
             "handback_plan %.4f handback_run %.4f\n", p->xh_s[0], p->xh_s[1], p->xh_s[2], p->xh_s[3], p->xh_s[4],
