@@ -508,6 +508,9 @@ int plan_alloc(int64_t n, const int64_t* row_ptr, const int32_t* colx, uint32_t 
       p->sv_reseed = !(s10 && atoi(s10) == 0);
       const char* s11 = getenv("PPR_SV_RESEED_BUDGET");
       if (s11) p->sv_reseed_budget = std::max(0, std::min(SV_XT_BUDGET, atoi(s11)));
+      p->sv_retry_mode = sv_retry_mode_parse(getenv("PPR_SV_RETRY_GRID"));
+      const char* s12 = getenv("PPR_SV_SEEDLESS");
+      if (s12) p->sv_seedless = atoi(s12) != 0;
       // Streams of the exact sum: a process has 4 hardware queues (HIP's default), and streams
       // beyond them share queues -- a kernel then waits behind another stream's kernel. The hot
       // pass's stream5 is unused here (no hot pass), so it goes, and each of the 4 remaining streams
@@ -1755,7 +1758,13 @@ struct SvRun {
   size_t o_ovl = 0;          // offset of the overflow list in d_sv
   size_t o_os = 0;           // ... and of the small class's first overflows (redone on the device)
   size_t o_om = 0;           // ... and of the mid class's (redone on the device, large geometry)
-  size_t o_cnt = 0;          // ... and of the re-seeding counters (seeded attempts, completed)
+  size_t o_ol = 0;           // ... and of the large class's (retried on the device, re-seeded)
+  size_t o_cnt = 0;          // ... and of the re-seeding counters (merge_sv.h SvSeed::cnt, SVC_N words)
+  int part = 0;              // the partition updated (ppr_plan::sv_hist)
+  // blocks of the retry launch behind the large class, the mid class (PPR_SV_REDO_LARGE=1) and the
+  // multi-slice chain (nm: queued); 0: skipped by the grid rule; -1: the list has no retry at all
+  int64_t grid[SvHist::NLIST] = {-1, -1, -1};
+  int64_t cnt[SvHist::NLIST] = {0, 0, 0};  // ... and the sources of the class it stands behind
   size_t cls_end[4] = {0, 0, 0, 0};  // descriptor index ends: multi-slice, large, mid, small
   bool live = false;
 };
@@ -1833,7 +1842,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   const size_t o_om = off; off = al(off + 4 * (1 + nx));  // mid class's first overflows (device redo)
   const size_t o_ol = off; off = al(off + 4 * (1 + nx));  // large class's first overflows (seeded retry)
   const size_t o_sn = off; off = al(off + 4 * nx);
-  const size_t o_cn = off; off = al(off + 16);
+  const size_t o_cn = off; off = al(off + 4 * SVC_N);
   const size_t o_of = off; off = al(off + 4 * (nm + 1));
   const size_t o_mk = off; off = al(off + 4 * (nm + 1));            // multi-slice: descriptors marked for the retry
   const size_t o_sd = off; off = al(off + 4 * (size_t)Lp * (nm + 1));  // ... and their seeds (Lp a descriptor)
@@ -1886,6 +1895,17 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   unsigned long long* d_ga = (unsigned long long*)(b + o_ga);
   unsigned long long* d_gb = (unsigned long long*)(b + o_gb);
   const size_t lds = sv_lds_bytes(Lp, SV_LARGE);
+  // retry grids from this partition's overflow history (sv_plan.h)
+  run.part = a.active == 1 ? 1 : 0;
+  for (int k = 0; k < SvHist::NLIST; k++) run.grid[k] = -1;
+  const SvHist& hist = p->sv_hist[run.part];
+  auto retry_grid = [&](int list, size_t cnt) {
+    const int64_t gr = hist.grid(list, (int64_t)cnt, p->sv_retry_mode);
+    run.grid[list] = gr;
+    run.cnt[list] = (int64_t)cnt;
+    (gr > 0 ? p->sv_retry_launched : p->sv_retry_skipped)++;
+    return gr;
+  };
   {
     // one-slice classes beside the multi-slice chain (stream_sv): large on stream_sv2, mid then
     // small on stream_sv3 (the mid class ends long before the large one; the small class's 40-KB
@@ -1912,26 +1932,29 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
       // the large class's overflows are retried with the same geometry, re-seeded (there is no larger
       // one: without seeds the retry would overflow again)
       const bool redo_s = c == 0 && seed_on(G);
+      // the k_sv1_list grid (one block per overflow) from the partition's overflow history; 0: no
+      // retry launch, the class runs as with re-seeding off and only counts its overflows
+      const int64_t gl = (redo_l || redo_s) ? retry_grid(c == 0 ? SvHist::LARGE : SvHist::MID, cnt_c) : -1;
       // the list the class's first overflows go to, and (`on`) with seeds for the retry behind it
-      int32_t* first = redo ? d_os : redo_l ? d_om : redo_s ? d_ol : nullptr;
+      int32_t* first = redo ? d_os : gl <= 0 ? nullptr : redo_l ? d_om : d_ol;
       const int on = first && seed_on(G) ? 1 : 0;
-      const SvSeed sd1{on ? first : nullptr, d_cn, on, 0};
+      const SvSeed sd1{on ? first : nullptr, d_cn, on, 0,
+                       gl == 0 ? d_cn + (c == 0 ? SVC_MISS_LARGE : SVC_MISS_MID) : nullptr};
       hipLaunchKernelGGL(k_sv1, dim3((unsigned)cnt_c), dim3(G.threads()), sv_lds_bytes(Lp, G), cs[c], g, s, a, d_v, d0,
-                         Lp, G, std::min(p->sv_budget, G.budget), (redo || redo_l) ? first : d_ov, d_ok, d_ovv, d_on,
-                         sd1);
+                         Lp, G, std::min(p->sv_budget, G.budget), ((redo || redo_l) && first) ? first : d_ov, d_ok,
+                         d_ovv, d_on, sd1);
       HIP_OK(hipGetLastError());
-      if (redo_l || redo_s) {
-        // (grid: the class overflows ~7 % of its sources at RMAT-22; past the grid the host takes them)
-        const unsigned gl = (unsigned)std::min<size_t>(cnt_c, cnt_c / 8 + 64);
-        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_LARGE)};
-        hipLaunchKernelGGL(k_sv1_list, dim3(gl), dim3(SV_LARGE.threads()), sv_lds_bytes(Lp, SV_LARGE), cs[c],
+      if (gl > 0) {
+        // (past the grid the host takes the overflows: k_sv1_list)
+        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_LARGE), nullptr};
+        hipLaunchKernelGGL(k_sv1_list, dim3((unsigned)gl), dim3(SV_LARGE.threads()), sv_lds_bytes(Lp, SV_LARGE), cs[c],
                            g, s, a, d_v, first, Lp, SV_LARGE, std::min(p->sv_budget, SV_LARGE.budget), d_ov, d_ok, d_ovv,
                            d_on, sd2);
         HIP_OK(hipGetLastError());
         p->merge_launches++;
       }
       if (redo) {
-        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_MID)};
+        const SvSeed sd2{nullptr, d_cn, on, seed_budget(SV_MID), nullptr};
         hipLaunchKernelGGL(k_sv1_redo, dim3((unsigned)std::min<size_t>(cnt_c, 512)), dim3(SV_MID.threads()),
                            sv_lds_bytes(Lp, SV_MID), cs[c], g, s, a, d_v, d_os, Lp, SV_MID,
                            std::min(p->sv_budget, SV_MID.budget), d_ov, d_ok, d_ovv, d_on, sd2);
@@ -1951,7 +1974,11 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
     kst_begin(p, 4, s1);
     // the chain, and (re-seeding on) once more for the descriptors whose first attempt overflowed:
     // k_svS marks them and writes their seeds, every other block of the second chain leaves at once
-    const SvSeed rs{d_mk, d_cn, seed_on(SV_LARGE) ? 1 : 0, seed_budget(SV_LARGE)};
+    // The retry chain is queued only where the grid rule asks for one; without it the first chain
+    // runs as with re-seeding off (no flush of overflowed slices, no k_svS) and counts its overflows.
+    const bool rs_can = seed_on(SV_LARGE);
+    const int64_t gm = rs_can ? retry_grid(SvHist::MULTI, nm) : -1;
+    const SvSeed rs{d_mk, d_cn, gm > 0 ? 1 : 0, seed_budget(SV_LARGE), gm == 0 ? d_cn + SVC_MISS_MULTI : nullptr};
     for (int retry = 0; retry <= rs.on; retry++) {
       hipLaunchKernelGGL(k_svA, dim3((unsigned)nt), dim3(SV_THREADS), lds, s1, g, s, a, d_d, d_t, Lp, d_sk, d_pt, rs,
                          d_sd, retry);
@@ -1977,6 +2004,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   run.o_ovl = o_ov;
   run.o_os = o_os;
   run.o_om = o_om;
+  run.o_ol = o_ol;
   run.o_cnt = o_cn;
   run.cls_end[0] = nm;
   for (int c = 0; c < 3; c++) run.cls_end[1 + c] = cls_end[c];
@@ -1997,8 +2025,9 @@ static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
     HIP_OK(hipEventRecord(p->ev_sv, p->stream_sv3));
     HIP_OK(hipStreamWaitEvent(p->stream_sv, p->ev_sv, 0));
   }
-  int32_t novf = 0, nsm = 0, nmd = 0, nrs[2] = {0, 0};
-  HIP_OK(hipMemcpyAsync(nrs, p->d_sv + run.o_cnt, 8, hipMemcpyDeviceToHost, p->stream_sv));
+  int32_t novf = 0, nsm = 0, nmd = 0, nlg = 0, nrs[SVC_N] = {};
+  HIP_OK(hipMemcpyAsync(nrs, p->d_sv + run.o_cnt, 4 * SVC_N, hipMemcpyDeviceToHost, p->stream_sv));
+  HIP_OK(hipMemcpyAsync(&nlg, p->d_sv + run.o_ol, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&novf, p->d_sv + run.o_ovl, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&nsm, p->d_sv + run.o_os, 4, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipMemcpyAsync(&nmd, p->d_sv + run.o_om, 4, hipMemcpyDeviceToHost, p->stream_sv));
@@ -2006,6 +2035,21 @@ static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
   p->sv_redo_dev += nsm + nmd;
   p->sv_reseed_n += nrs[0];
   p->sv_reseed_ok += nrs[1];
+  p->sv_seedless_n += nrs[SVC_SEEDLESS];
+  p->sv_seedless_done += nrs[SVC_SEEDLESS_DONE];
+  {
+    // first overflows of the retried lists in this update: those that reached a list (retried, or
+    // past its grid) and those counted where the retry was skipped. They size the next update's grids.
+    const int64_t first[SvHist::NLIST] = {(int64_t)nlg + nrs[SVC_MISS_LARGE],
+                                          (run.grid[SvHist::MID] > 0 ? (int64_t)nmd : 0) + nrs[SVC_MISS_MID],
+                                          (int64_t)nrs[SVC_MULTI] + nrs[SVC_MISS_MULTI]};
+    for (int k = 0; k < SvHist::NLIST; k++) {
+      if (run.grid[k] < 0) continue;
+      p->sv_hist[run.part].push(k, first[k], run.cnt[k]);
+      // (the chain retries every marked source: a multi-slice overflow misses only a skipped chain)
+      p->sv_past_grid += run.grid[k] == 0 ? first[k] : k == SvHist::MULTI ? 0 : std::max<int64_t>(0, first[k] - run.grid[k]);
+    }
+  }
   for (int g = 1; g < ppr_plan::NKST; g++) kst_fold(p, g);
   if (!novf) return PPR_OK;
   std::vector<int32_t> od(novf);
@@ -2090,9 +2134,27 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   };
   src.reserve(nh); cand.reserve(nh); deg.reserve(nh); dest.reserve(nh);
   if (sieve) { ssrc.reserve(nh); scand.reserve(nh); sdeg.reserve(nh); sidx.reserve(nh); }
+  // A source whose current row is short (a partition's first real updates) has a seedless first
+  // attempt in the sieve (merge_sv.h) where a seeded retry stands behind its launch: re-seeding on at
+  // the small class's geometry (the smallest table), one slice, and a class with a device retry --
+  // the small class (its redo), the large class, the mid class only with PPR_SV_REDO_LARGE=1. Such a
+  // source has deg + 1 < L successors' rows: at most (L - 2) L + 1 candidates.
+  const bool seedless = sieve && p->sv_seedless && p->sv_reseed && std::min(p->sv_budget, SV_SMALL.budget) >= p->Lp;
+  // (and a retry launch that this update's grid rule does not skip: sv_plan.h)
+  const SvHist& hist = p->sv_hist[a.active == 1 ? 1 : 0];
+  auto retried = [&](int list) {
+    return hist.grid(list, 1, p->sv_retry_mode) > 0;
+  };
+  const bool short_large = seedless && retried(SvHist::LARGE);
+  const bool short_mid = seedless && p->sv_redo_large && retried(SvHist::MID);
+  auto short_ok = [&](int64_t c) {
+    if (c > p->sv_slice) return false;
+    return c >= p->sv_mid ? short_large : c >= p->sv_small ? short_mid : p->sv_redo_mid;
+  };
   for (size_t i = 0; i < nh; i++) {
     const int32_t c = h[nh + i];
-    if (sieve && h[4 * nh + i] == (int32_t)p->L && c >= p->sv_min && c < (1 << 30)) {
+    if (sieve && c >= p->sv_min && c < (1 << 30) &&
+        (h[4 * nh + i] == (int32_t)p->L || (seedless && short_ok(c)))) {
       ssrc.push_back(h[i]);
       scand.push_back(c);
       sdeg.push_back(h[2 * nh + i]);
@@ -2106,6 +2168,7 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   }
   lap(1, tl);  // classification
   SvRun run;
+  const int64_t rl0 = p->sv_retry_launched, rp0 = p->sv_retry_skipped;  // (PPR_SV_LOG: this call's)
   // the larger of the two host plannings goes second: when the range engines take more sources
   // than the sieve (the big partition's iterations: ~258 K mid-sized sources at RMAT-22), they are
   // planned and queued first and collected after the sieve's launches (PPR_XH_FIRST=0: sieve first)
@@ -2125,6 +2188,7 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   std::vector<int32_t>& back = p->xhs.back;
   back.clear();
   const int64_t dev0 = p->sv_redo_dev, rs0 = p->sv_reseed_n, rk0 = p->sv_reseed_ok;
+  const int64_t pg0 = p->sv_past_grid, sl0 = p->sv_seedless_n, sd0 = p->sv_seedless_done;
   { int r = sieve_collect(p, run, back); if (r) return r; }
   lap(4, tl);  // waiting for the sieve
   if (getenv("PPR_SV_LOG")) {
@@ -2142,9 +2206,13 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
     }
     for (int32_t c : scand) sc += c;
     fprintf(stderr, "ppr_sv_log it %d sieved %zu range %zu dev_redo %lld handed_back %zu sieved_cand %lld "
-            "hb_large %lld %lld hb_mid %lld %lld hb_small %lld %lld hb_multi %lld %lld reseed %lld reseed_ok %lld\n",
+            "hb_large %lld %lld hb_mid %lld %lld hb_small %lld %lld hb_multi %lld %lld reseed %lld reseed_ok %lld "
+            "retry_launched %lld retry_skipped %lld past_grid %lld seedless %lld seedless_done %lld\n",
             a.iter, ssrc.size(), src.size(), (long long)(p->sv_redo_dev - dev0), back.size(), sc, hn[1], hc[1], hn[2],
-            hc[2], hn[3], hc[3], hn[0], hc[0], (long long)(p->sv_reseed_n - rs0), (long long)(p->sv_reseed_ok - rk0));
+            hc[2], hn[3], hc[3], hn[0], hc[0], (long long)(p->sv_reseed_n - rs0), (long long)(p->sv_reseed_ok - rk0),
+            (long long)(p->sv_retry_launched - rl0), (long long)(p->sv_retry_skipped - rp0),
+            (long long)(p->sv_past_grid - pg0), (long long)(p->sv_seedless_n - sl0),
+            (long long)(p->sv_seedless_done - sd0));
   }
   if (back.empty()) return PPR_OK;
   // handed back: the range / partition engines, with the usual estimate
@@ -2535,6 +2603,7 @@ extern "C" int ppr_grank_plan_init(ppr_plan* p) {
   // every job plans from its own merges only: the range engines' distinct-key estimates (d_dlast,
   // the last merge's count) start over, so a repeated run is a cold call
   if (p->d_dlast) HIP_OK(hipMemsetAsync(p->d_dlast, 0, 4 * (size_t)std::max<int64_t>(1, p->n), p->stream));
+  p->sv_hist[0] = p->sv_hist[1] = SvHist{};  // (and the sieve's retry grids from its own overflows only)
   IterArgs a = iter_args(p, 0, true);
   int rc = init_dangling(p, p->d_all + p->n_nd, p->n - p->n_nd);
   if (rc) return rc;
@@ -3320,6 +3389,7 @@ static int init_sharded(ppr_plan* p, const std::vector<int64_t> (&bd)[2], const 
   p->hot_n = 0;
   p->hot_built_it = -1;
   if (p->d_dlast) HIP_OK(hipMemsetAsync(p->d_dlast, 0, 4 * (size_t)std::max<int64_t>(1, p->n), s));
+  p->sv_hist[0] = p->sv_hist[1] = SvHist{};
   IterArgs a = iter_args(p, 0, true);
   int rc = init_dangling(p, p->d_all + p->n_nd, p->n - p->n_nd);
   if (rc) return rc;

@@ -27,8 +27,13 @@
 // attempt builds PT from the seeds: the same algorithm with a bound theta' >= theta, the same
 // bit-exact row. Seeds are written only when the table's budget is at least Lp (a smaller table
 // cannot improve on PT). A second overflow, or a first one with re-seeding off, hands the source
-// back to the range / partition engines of merge_xs.h (correct either way, slower). Sources whose
-// current row is not full (no L keys to bound with) never enter the sieve.
+// back to the range / partition engines of merge_xs.h (correct either way, slower). A source whose
+// current row is not full has no L keys to bound with; theta = 0 is trivially valid for it. Where a
+// seeded retry stands behind its launch (PPR_SV_SEEDLESS, one-slice classes) its first attempt runs
+// "seedless": PT is the short row, every other key passes, and the attempt either fits the table --
+// a complete exact merge -- or overflows and seeds its retry like any other. Elsewhere (multi-slice
+// sources, a class without a retry) such a source is handed back at once, as before.
+// The retry launches are sized on the host from the partition's own overflow counts (sv_plan.h).
 //
 // Exact accumulators: X = sum floor(p * 2^93) (oracle/grank_oracle.c "exact") held as two u64
 // words that are only ever added to -- A = sum of the low 32 bits of each X_i, B = sum of X_i >> 32
@@ -367,14 +372,15 @@ __device__ __forceinline__ void sv_build_pt_keys(const SvLds& x, int n, KeyAt ke
     }
   }
 }
-// PT of source v: the L keys of its current row, or (a seeded attempt, `seeds` != nullptr) the L
-// seed keys an overflowed first attempt wrote
+// PT of source v: the keys of its current row (L, or fewer in a seedless attempt), or (a seeded
+// attempt, `seeds` != nullptr) the L seed keys an overflowed first attempt wrote -- always L of
+// them, whatever the row's length (a seedless attempt's row is short, its seeds are not)
 __device__ __forceinline__ void sv_build_pt(const SvLds& x, const DevSlab& s, const IterArgs& a, int v, int Lp,
                                             const int32_t* seeds = nullptr) {
   const int cur = (a.active == 1) ? a.sB : a.sA;
   const int64_t r = s.row(cur, v);
-  const int len = s.len[s.lrow(cur, v)];
-  sv_build_pt_keys(x, len, [&](int i) { return seeds ? (int)seeds[i] : s.key(s.ids[r + i]); });
+  const int n = seeds ? s.L : s.len[s.lrow(cur, v)];
+  sv_build_pt_keys(x, n, [&](int i) { return seeds ? (int)seeds[i] : s.key(s.ids[r + i]); });
 }
 
 // The wave's share of a slice: contiguous successors [c0, c1) taken row by row. Row metadata comes
@@ -748,10 +754,17 @@ constexpr int32_t SV_SEEDED = -1;
 struct SvSeed {
   int32_t* retry;   // one-slice: the list a seeded source is appended to ([0] count, [1..] descriptors);
                     // nullptr: no retry runs behind this launch. Multi-slice: the per-descriptor marks.
-  int32_t* cnt;     // [0] seeded attempts, [1] those that completed
+  int32_t* cnt;     // [0] seeded attempts, [1] those that completed, [2] multi-slice sources k_svS marked,
+                    // [SVC_SEEDLESS] first attempts without a full row, [SVC_SEEDLESS_DONE] those written
   int32_t on;       // seeds are written and used (PPR_SV_RESEED, and a table budget of at least Lp)
   int32_t budget;   // table budget of a seeded attempt (PPR_SV_RESEED_BUDGET; 0: it always overflows)
+  int32_t* miss;    // the retry behind this launch was skipped (sv_plan.h: no overflow in the last two
+                    // updates): its first overflows go to the host unseeded and are counted here, so the
+                    // next update's grid sees them; nullptr otherwise
 };
+// SvSeed::cnt slots past the three above (host: sieve_launch zeroes and sieve_collect reads SVC_N words)
+enum { SVC_MULTI = 2, SVC_MISS_LARGE = 3, SVC_MISS_MID = 4, SVC_MISS_MULTI = 5, SVC_SEEDLESS = 6, SVC_SEEDLESS_DONE = 7,
+       SVC_N = 8 };
 
 // one source (descriptor d) of a one-slice class, the whole workgroup; a source that overflows
 // (or has no full row) goes to `ovl` and writes nothing -- or, a first overflow with a retry behind
@@ -767,8 +780,14 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   // a seeded attempt: PT from the seeds the first attempt left in `ok` (workgroup-uniform)
   const bool seeded = sd.on && out_n[d] == SV_SEEDED;
   if (seeded) budget = sd.budget;
-  // (the host sends only sources with a full current row: L keys to bound with)
-  if (s.len[s.lrow((a.active == 1) ? a.sB : a.sA, v)] != L) {
+  // A current row that is not full has no L keys to bound with, and needs none: theta = 0 is a valid
+  // bound for it. With a seeded retry behind this launch the attempt runs "seedless" -- PT is the
+  // short row, every other key passes -- and either fits the table (a complete exact merge) or
+  // overflows and seeds its retry like any other first attempt. Without a retry behind it the
+  // source goes to `ovl` at once, as it always did. (Workgroup-uniform.)
+  const bool shortrow = s.len[s.lrow((a.active == 1) ? a.sB : a.sA, v)] != L;
+  const bool seedless = shortrow && !seeded && sd.on && sd.retry != nullptr;
+  if (shortrow && !seeded && !seedless) {
     if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
     return;
   }
@@ -783,6 +802,7 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
     *reinterpret_cast<unsigned long long*>(&x.misc[SVM_THETA]) = ~0ull;
     sv_seed1(x, v, 1.0 - a.damping, sk);
     if (seeded) atomicAdd(&sd.cnt[0], 1);
+    if (seedless) atomicAdd(&sd.cnt[SVC_SEEDLESS], 1);
   }
   sv_lap(a, dg + 0, tph);
   const int64_t b = g.rp[v], e = g.rp[v + 1];
@@ -794,9 +814,10 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
   sv_lap(a, dg + 1, tph);
   // bound: the smallest exact total of the L prev keys
   const int Tpt = x.pt.T;
-  const double theta = sv_theta(x, Tpt, [&](int i) {
+  const double theta_pt = sv_theta(x, Tpt, [&](int i) {
     return (x.pt.keys[i] & ~SV_OVF_BIT) ? x2_value(x.pt.ab[2 * i], x.pt.ab[2 * i + 1]) : bitsd(~0ull >> 1);  // (empty: above every value)
   });
+  const double theta = seedless ? 0.0 : theta_pt;  // (fewer than L exact totals bound nothing)
   const uint32_t thr = sv_thr(theta);
   sv_bitmap(x, thr, [&](int c) { return sk[c]; });
   __syncthreads();
@@ -820,6 +841,7 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
     if (threadIdx.x == 0) {
       ovl[1 + atomicAdd(&ovl[0], 1)] = d;
       if (seeded) out_n[d] = 0;  // (k_svfin: handed back)
+      else if (sd.miss) atomicAdd(sd.miss, 1);  // (a first overflow whose retry launch was skipped)
     }
     if (a.diag && threadIdx.x == 0) { diag_add(a.diag, 137, 1ull); diag_add(a.diag, dg + 7, 1ull); }
     return;
@@ -907,6 +929,7 @@ __device__ __forceinline__ void sv1_source(unsigned char* smem, DevGraph g, DevS
     } else {
       out_n[d] = x.misc[SVM_PT];
       if (seeded) atomicAdd(&sd.cnt[1], 1);
+      if (shortrow) atomicAdd(&sd.cnt[SVC_SEEDLESS_DONE], 1);
     }
   }
   if (threadIdx.x == 0) sv_lap(a, dg + 4, tph);
@@ -1159,7 +1182,7 @@ __global__ void __launch_bounds__(256) k_svS(DevSlab s, IterArgs a, const SvDesc
   uint32_t* gs = gsk + sd.gsk;
   for (int i = threadIdx.x; i < SV_R * (1 << SV_LARGE.wlog); i += blockDim.x) gs[i] = 0u;
   for (int i = threadIdx.x; i < sd.tg; i += blockDim.x) { gk[i] = 0u; gA[i] = 0ull; gB[i] = 0ull; }
-  if (threadIdx.x == 0) { rs.retry[d] = 1; oflag[d] = 0; }
+  if (threadIdx.x == 0) { rs.retry[d] = 1; oflag[d] = 0; atomicAdd(&rs.cnt[SVC_MULTI], 1); }
 }
 
 // k_svF LDS: dense values f64[SVF_CAP + Lp] | keys i32[SVF_CAP + Lp] | misc | finish_source scratch
@@ -1192,7 +1215,10 @@ __global__ void __launch_bounds__(256) k_svF(DevSlab s, IterArgs a, const SvDesc
   if (oflag[d] || !full) {
     // (a first overflow that k_svS will seed for the retry chain stays off the hand-back list)
     if (!sv_seeds_multi(oflag[d] != 0, full, retry, rs, sd)) {
-      if (threadIdx.x == 0) ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+      if (threadIdx.x == 0) {
+        ovl[1 + atomicAdd(&ovl[0], 1)] = d;
+        if (rs.miss && oflag[d] && full && !retry) atomicAdd(rs.miss, 1);  // (the retry chain was skipped)
+      }
     }
     return;
   }

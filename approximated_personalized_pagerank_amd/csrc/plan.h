@@ -10,6 +10,7 @@
 
 #include "../../include/ppr_hip.h"
 #include "ppr_common.h"
+#include "sv_plan.h"
 
 using namespace pprk;
 
@@ -267,6 +268,11 @@ struct ppr_plan {
   bool sv_reseed = true;              // PPR_SV_RESEED=0: an overflowed source is handed on as before, no seeded retry
   int sv_reseed_budget = -1;          // PPR_SV_RESEED_BUDGET (tests): table budget of the seeded attempts only
                                       // (0: every seeded attempt overflows); -1: the attempt's usual budget
+  int sv_retry_mode = SV_GRID_AUTO;   // PPR_SV_RETRY_GRID: auto | legacy | full | N blocks (sv_plan.h sv_retry_grid)
+  bool sv_seedless = false;           // PPR_SV_SEEDLESS=1: sources whose current row is short get a theta = 0 first
+                                      // attempt in the sieve (opt-in: at RMAT-22 they all overflow the small
+                                      // class's table and pay three passes, +5.7 ms per job)
+  SvHist sv_hist[2];                  // this job's first-overflow counts per partition (reset by every init)
   int64_t sv_small = 32768, sv_mid = 65536;  // PPR_SV_SMALL / PPR_SV_MID: one-slice size classes by candidates
                                       // (same-box sweep of SV_SMALL 16 K / 32 K / 48 K / 64 K: 1632 / 1589-1594 /
                                       // 1593 / 1664 ms per job; SV_MID 32 K / 131 K: +-0)
@@ -280,6 +286,9 @@ struct ppr_plan {
   int64_t sv_sources = 0, sv_redo = 0;  // sieved sources, handed back after an overflow (PPR_TIMING)
   int64_t sv_redo_dev = 0;            // small / mid-class overflows redone on the device (mid / large geometry)
   int64_t sv_reseed_n = 0, sv_reseed_ok = 0;  // seeded attempts (every class, multi-slice too), those that completed
+  // retry launches / chains queued and skipped by the grid rule, first overflows that found no retry
+  // block, first attempts run without a full row and those whose row the sieve wrote (PPR_TIMING)
+  int64_t sv_retry_launched = 0, sv_retry_skipped = 0, sv_past_grid = 0, sv_seedless_n = 0, sv_seedless_done = 0;
   double xh_s[8] = {};                // run_xhubs host sections, s (PPR_TIMING at destroy)
   // preference-set queries (query.hip): grow-only scratch of one chunk, kept across calls
   unsigned char* d_q = nullptr;       // query arrays, planner verdicts, tier lists, outputs
@@ -350,6 +359,10 @@ inline void plan_free(ppr_plan* p) {
     fprintf(stderr, "ppr_timing sieve_sources %lld sieve_redo %lld sieve_redo_dev %lld sieve_reseed %lld "
             "sieve_reseed_ok %lld\n", (long long)p->sv_sources, (long long)p->sv_redo, (long long)p->sv_redo_dev,
             (long long)p->sv_reseed_n, (long long)p->sv_reseed_ok);
+  if (getenv("PPR_TIMING") && p->sv_sources)
+    fprintf(stderr, "ppr_timing sieve_retry launched %lld skipped %lld past_grid %lld seedless %lld seedless_done %lld\n",
+            (long long)p->sv_retry_launched, (long long)p->sv_retry_skipped, (long long)p->sv_past_grid,
+            (long long)p->sv_seedless_n, (long long)p->sv_seedless_done);
   if (getenv("PPR_TIMING") && p->sv_sources)
     fprintf(stderr, "ppr_timing xhubs_host_s gather %.4f classify %.4f sieve_launch %.4f engines %.4f sieve_wait %.4f "
             "handback_plan %.4f handback_run %.4f\n", p->xh_s[0], p->xh_s[1], p->xh_s[2], p->xh_s[3], p->xh_s[4],
