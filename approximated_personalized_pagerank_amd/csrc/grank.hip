@@ -200,7 +200,9 @@ int plan_alloc(int64_t n, const int64_t* row_ptr, const int32_t* colx, uint32_t 
   TRY(dalloc(&p->d_tier_cap, NT + 1));
   TRY(dalloc(&p->d_ovf, n));
   TRY(dalloc(&p->d_maxdiff, PPR_MAX_ITER_STATS + 1));
-  TRY(dalloc(&p->d_stats, PPR_NSTATS));
+  TRY(dalloc(&p->d_stats, PPR_NSTATS_ALL));
+  // (a run zeroes its PPR_NSTATS counters; the length-change shards behind them only count up)
+  TRY(hipMemset(p->d_stats, 0, 8 * PPR_NSTATS_ALL) == hipSuccess ? PPR_OK : PPR_ERR_HIP);
   TRY(dalloc(&p->d_out_ids, (size_t)n * K));
   TRY(dalloc(&p->d_out_sc, (size_t)n * K));
   TRY(dalloc(&p->d_out_len, n));
@@ -303,6 +305,8 @@ int plan_alloc(int64_t n, const int64_t* row_ptr, const int32_t* colx, uint32_t 
     if (ent) p->nt_loads = (int)strtol(ent, nullptr, 0) & 3;
     const char* ewi = getenv("PPR_WHATIF");
     if (ewi) p->whatif = (int)strtol(ewi, nullptr, 0);
+    const char* erpl = getenv("PPR_REPLAY");  // 0: every update classifies and plans afresh
+    if (erpl) p->replay = atoi(erpl) != 0;
     const char* ebd = getenv("PPR_WAVE_BY_D");  // exact sum: wave tiers sized by the last distinct-key count
     if (ebd) p->wave_by_d = atoi(ebd) != 0;
     const char* etd = getenv("PPR_WAVE_TDIV");  // tests: wave-tier tables T >> this (bounded probes run out)
@@ -805,6 +809,15 @@ static IterArgs iter_args(const ppr_plan* p, int it, bool unit) {
 
 static int run_merge_impl(ppr_plan* p, const IterArgs& a, const int32_t* list, int64_t count,
                           unsigned long long* maxdiff);
+static inline ReplayKnobs replay_knobs(const ppr_plan* p) {
+  ReplayKnobs k;
+  k.enabled = p->replay;
+  k.sharded = p->replay_sharded || p->comm != nullptr || p->lgroup != nullptr || p->nranks > 1;
+  k.wave_by_d = p->wave_by_d;
+  k.sv_seedless = p->sv_seedless;
+  k.hot = p->hot_cap > 0 || p->hot_n > 0;
+  return k;
+}
 
 static int ensure_scratch(ppr_plan* p, size_t need) {
   if (need <= p->scratch_bytes) return PPR_OK;
@@ -1437,7 +1450,8 @@ struct XhDefer {
   const std::vector<int32_t>* cand = nullptr;
   const std::vector<int32_t>* deg = nullptr;
   const std::vector<int64_t>* dest = nullptr;
-  std::vector<int32_t> xv;
+  std::vector<int32_t> xv;                  // source of each descriptor
+  const std::vector<int32_t>* xvp = nullptr;  // ... held by a recorded plan instead (XrPlan::xv)
 };
 static int xhubs_finish(ppr_plan* p, const IterArgs& a, XhDefer& df, unsigned long long* maxdiff);
 
@@ -1448,24 +1462,98 @@ static inline void sub_lap(ppr_plan* p, int k, std::chrono::steady_clock::time_p
   t = t2;
 }
 
+// workgroup table classes of the range engines (slots, waves): 16 waves per CU in each
+struct XrCls { int T, W; };
+static inline void xr_classes(const ppr_plan* p, XrCls (&cls)[3]) {
+  // (T / 512 waves: the epilogue settles XR_SLOTS = 8 slots per thread)
+  cls[0] = XrCls{std::min(2048, p->xr_T), std::min(2048, p->xr_T) / 512};
+  cls[1] = XrCls{std::min(4096, p->xr_T), std::min(4096, p->xr_T) / 512};
+  cls[2] = XrCls{p->xr_T, p->xr_T / 512};
+}
+
+// The launching half of run_xhubs_list: the range engines of plan P (descriptors and tasks already
+// on the device at P.d_up) queued on stream3, their work areas in d_xs zeroed first. A replayed
+// update runs only this.
+static int xr_queue(ppr_plan* p, const IterArgs& a, const XrPlan& P, unsigned long long* maxdiff) {
+  hipStream_t sw = p->stream3 ? p->stream3 : p->stream;
+  DevGraph g{p->d_rp, p->d_colx, p->n};
+  const DevSlab s = dev_slab(p);
+  XrCls cls[3];
+  xr_classes(p, cls);
+  {
+    int rc = ensure_dev(&p->d_xs, &p->xs_bytes, P.total);
+    if (rc) return rc;
+  }
+  unsigned char* b = p->d_xs;
+  const XDesc* d_xd = (const XDesc*)(P.d_up + P.o_d);
+  const XTask* d_tk = (const XTask*)(P.d_up + P.o_t);
+  int32_t* d_pk = (int32_t*)(b + P.o_k);
+  double* d_ps = (double*)(b + P.o_s);
+  uint32_t* d_pc = (uint32_t*)(b + P.o_pc);
+  uint32_t* d_ds = (uint32_t*)(b + P.o_ds);
+  int32_t* d_of = (int32_t*)(b + P.o_of);
+  int32_t* d_ov = (int32_t*)(b + P.o_ov);
+  unsigned long long* d_xt = (unsigned long long*)(b + P.o_xt);
+  HIP_OK(hipMemsetAsync(b + P.o_z, 0, P.total - P.o_z, sw));
+  // kernel-stat group 5: the range engines (k_xr, k_xfinal, k_xfin1) of this call on sw; SURVEY
+  // s8d bytes with the rows at min(L, candidates + 1) entries (the host knows no row lengths)
+  if (!a.unit && !a.mc) {
+    kst_begin(p, 5, sw);
+    p->kst_pend_bytes[5] = P.bytes;
+  }
+  const bool big_first = p->xr_big_first;  // (experiment)
+  if (P.nxm) {
+    const int T = cls[0].T, W = cls[0].W;
+    const int budget = p->xr_budget_over ? 2 * T : std::min(T * 85 / 100, T - W * WAVE - WAVE);
+    // (4 waves: 8 waves at 3 workgroups per CU would need more than 80 VGPRs)
+    hipLaunchKernelGGL(k_xm<4>, dim3((unsigned)P.nxm), dim3(64 * 4), xm_lds_bytes(T), sw, g, s, a,
+                       (const XmTask*)(P.d_up + P.o_m), T, budget, d_pk, d_ps, d_pc, d_ds, d_of, d_ov);
+    HIP_OK(hipGetLastError());
+    p->merge_launches++;
+  }
+  for (int c0 = 0; c0 < 3; c0++) {
+    const int c = big_first ? 2 - c0 : c0;
+    if (!P.tcount[c]) continue;
+    const int T = cls[c].T, W = cls[c].W;
+    // (PPR_XR_BUDGET=over, tests: no budget stop -- the tables fill and the bounded probes run
+    // out, which must end in the overflow redo)
+    const int budget = p->xr_budget_over ? 2 * T : std::min(T * 85 / 100, T - W * WAVE - WAVE);
+    hipLaunchKernelGGL(k_xr, dim3((unsigned)P.tcount[c]), dim3(64 * W), xr_lds_bytes(T, W, p->Lp), sw, g, s, a,
+                       d_xd, d_tk + P.tofs[c], T, budget, p->Lp, d_xt, d_pk, d_ps, d_pc, d_ds, d_of, d_ov, p->xr_cap);
+    HIP_OK(hipGetLastError());
+    p->merge_launches++;
+  }
+  if (P.nmulti) {
+    hipLaunchKernelGGL(k_xfinal<XDesc>, dim3((unsigned)P.nmulti), dim3(256), xf_lds_bytes(p->Lp, p->xf_stage), sw, s, a,
+                       d_xd, d_xt, d_pk, d_ps, d_pc, d_ds, d_of, p->d_dlast, p->Lp, p->xf_stage, maxdiff, p->d_stats);
+    HIP_OK(hipGetLastError());
+    p->merge_launches++;
+  }
+  if (P.nx > P.nmulti) {
+    hipLaunchKernelGGL(k_xfin1, dim3((unsigned)(P.nx - P.nmulti)), dim3(64), xf1_lds_bytes(p->Lp), sw, s, a, d_xd,
+                       (int)P.nmulti, d_pk, d_ps, d_pc, d_ds, d_of, p->d_dlast, p->Lp, maxdiff, p->d_stats);
+    HIP_OK(hipGetLastError());
+    p->merge_launches++;
+  }
+  if (!a.unit && !a.mc) kst_end(p, 5, sw, p->kst_pend_bytes[5]);
+  return PPR_OK;
+}
+
+// `rec` (a recording update, run_xhubs): the plan is left in rec->xr with its descriptors in the
+// record's own device buffer, complete when rec->xr.simple
 static int run_xhubs_list(ppr_plan* p, const IterArgs& a, const std::vector<int32_t>& src,
                           const std::vector<int32_t>& cand, const std::vector<int32_t>& deg,
                           const std::vector<int64_t>& dest, unsigned long long* maxdiff, int depth,
-                          XhDefer* defer = nullptr) {
+                          XhDefer* defer = nullptr, XhRec* rec = nullptr) {
   const size_t n = src.size();
+  if (rec) rec->xr.simple = false;
   if (!n) return PPR_OK;
   auto tsub = std::chrono::steady_clock::now();
   hipStream_t st = p->stream;
   hipStream_t sw = p->stream3 ? p->stream3 : st;
-  DevGraph g{p->d_rp, p->d_colx, p->n};
-  const DevSlab s = dev_slab(p);
   const int64_t L = p->L;
-  // workgroup table classes (slots, waves): 16 waves per CU in each
-  struct Cls { int T, W; };
-  // (T / 512 waves: the epilogue settles XR_SLOTS = 8 slots per thread)
-  const Cls cls[3] = {{std::min(2048, p->xr_T), std::min(2048, p->xr_T) / 512},
-                      {std::min(4096, p->xr_T), std::min(4096, p->xr_T) / 512},
-                      {p->xr_T, p->xr_T / 512}};
+  XrCls cls[3];
+  xr_classes(p, cls);
   auto cap_of = [&](int T) { return (int64_t)T * p->xr_fill / 100; };
   // (per-thread scratch kept across calls: no page faults on fresh vectors each iteration; a call's
   // lists are dead before the nested redo call of its tail or of xhubs_finish reuses them)
@@ -1561,24 +1649,26 @@ static int run_xhubs_list(ppr_plan* p, const IterArgs& a, const std::vector<int3
   const size_t o_ov = off; off = al(off + 4 * (nx + 2));
   const size_t o_xt = off; off = al(off + 8 * (nx + 1));
   const size_t total = off;
-  std::vector<int32_t> ovl_h;
+  XrPlan lplan;
+  XrPlan& P = rec ? rec->xr : lplan;
+  P.n = n; P.nx = nx; P.nmulti = (size_t)nmulti; P.nxm = xmt.size(); P.ntask = ntask; P.pt = pt;
+  P.o_d = o_d; P.o_t = o_t; P.o_m = o_m; P.o_k = o_k; P.o_s = o_s; P.o_z = o_z; P.o_pc = o_pc; P.o_ds = o_ds;
+  P.o_of = o_of; P.o_ov = o_ov; P.o_xt = o_xt; P.total = total;
+  P.simple = nx && bsrc.empty() && xgs.empty();
   if (nx) {
     {
       int rc = ensure_dev(&p->d_xs, &p->xs_bytes, total);
       if (rc) return rc;
     }
-    unsigned char* b = p->d_xs;
-    XDesc* d_xd = (XDesc*)(b + o_d);
-    XTask* d_tk = (XTask*)(b + o_t);
-    int32_t* d_pk = (int32_t*)(b + o_k);
-    double* d_ps = (double*)(b + o_s);
-    uint32_t* d_pc = (uint32_t*)(b + o_pc);
-    uint32_t* d_ds = (uint32_t*)(b + o_ds);
-    int32_t* d_of = (int32_t*)(b + o_of);
-    int32_t* d_ov = (int32_t*)(b + o_ov);
-    unsigned long long* d_xt = (unsigned long long*)(b + o_xt);
     // descriptors and tasks through the pinned staging buffer (one upload)
     const size_t up = o_m + sizeof(XmTask) * xmt.size();
+    P.up = up;
+    P.d_up = p->d_xs;
+    if (rec && P.simple) {  // a complete plan keeps its descriptors in the record's own buffer
+      int rc = ensure_dev(&rec->d_xr_up, &rec->xr_up_bytes, up + 256);
+      if (rc) return rc;
+      P.d_up = rec->d_xr_up;
+    }
     {
       // (its own pinned buffer: run_hubs below restages h_desc_pin while this upload may be pending;
       // the previous upload from it completed at the last call's closing sync of sw)
@@ -1588,64 +1678,30 @@ static int run_xhubs_list(ppr_plan* p, const IterArgs& a, const std::vector<int3
     unsigned char* hb = (unsigned char*)p->h_xs_pin;
     std::memcpy(hb + o_d, xd.data(), sizeof(XDesc) * nx);
     if (!xmt.empty()) std::memcpy(hb + o_m, xmt.data(), sizeof(XmTask) * xmt.size());
-    size_t tofs[3];
     {
       size_t k = 0;
       for (int c = 0; c < 3; c++) {
-        tofs[c] = k;
+        P.tofs[c] = k;
+        P.tcount[c] = tasks[c].size();
         if (!tasks[c].empty()) std::memcpy(hb + o_t + sizeof(XTask) * k, tasks[c].data(), sizeof(XTask) * tasks[c].size());
         k += tasks[c].size();
       }
     }
     sub_lap(p, 2, tsub);  // range planning: staging
-    HIP_OK(hipMemcpyAsync(b, hb, up, hipMemcpyHostToDevice, sw));
-    HIP_OK(hipMemsetAsync(b + o_z, 0, total - o_z, sw));
-    // kernel-stat group 5: the range engines (k_xr, k_xfinal, k_xfin1) of this call on sw; SURVEY
-    // s8d bytes with the rows at min(L, candidates + 1) entries (the host knows no row lengths)
-    if (!a.unit && !a.mc) {
-      double bytes = 0.0;
+    HIP_OK(hipMemcpyAsync(P.d_up, hb, up, hipMemcpyHostToDevice, sw));
+    // SURVEY s8d bytes with the rows at min(L, candidates + 1) entries (the host knows no row lengths)
+    P.bytes = 0.0;
+    if (!a.unit && !a.mc)
       for (size_t i = 0; i < n; i++)
         if (rng[i] > 0)
-          bytes += 8.0 + 8.0 * deg[i] + 12.0 * ((double)cand[i] - 1.0) +
-                   24.0 * (double)std::min<int64_t>(L, (int64_t)cand[i] + 1) + 4.0;
-      kst_begin(p, 5, sw);
-      p->kst_pend_bytes[5] = bytes;
+          P.bytes += 8.0 + 8.0 * deg[i] + 12.0 * ((double)cand[i] - 1.0) +
+                     24.0 * (double)std::min<int64_t>(L, (int64_t)cand[i] + 1) + 4.0;
+    P.xv.resize(nx);
+    for (size_t i = 0; i < nx; i++) P.xv[i] = xd[i].v;
+    {
+      int rc = xr_queue(p, a, P, maxdiff);
+      if (rc) return rc;
     }
-    const bool big_first = p->xr_big_first;  // (experiment)
-    if (!xmt.empty()) {
-      const int T = cls[0].T, W = cls[0].W;
-      const int budget = p->xr_budget_over ? 2 * T : std::min(T * 85 / 100, T - W * WAVE - WAVE);
-      // (4 waves: 8 waves at 3 workgroups per CU would need more than 80 VGPRs)
-      hipLaunchKernelGGL(k_xm<4>, dim3((unsigned)xmt.size()), dim3(64 * 4), xm_lds_bytes(T), sw, g, s, a,
-                         (const XmTask*)(b + o_m), T, budget, d_pk, d_ps, d_pc, d_ds, d_of, d_ov);
-      HIP_OK(hipGetLastError());
-      p->merge_launches++;
-    }
-    for (int c0 = 0; c0 < 3; c0++) {
-      const int c = big_first ? 2 - c0 : c0;
-      if (tasks[c].empty()) continue;
-      const int T = cls[c].T, W = cls[c].W;
-      // (PPR_XR_BUDGET=over, tests: no budget stop -- the tables fill and the bounded probes run
-      // out, which must end in the overflow redo)
-      const int budget = p->xr_budget_over ? 2 * T : std::min(T * 85 / 100, T - W * WAVE - WAVE);
-      hipLaunchKernelGGL(k_xr, dim3((unsigned)tasks[c].size()), dim3(64 * W), xr_lds_bytes(T, W, p->Lp), sw, g, s, a,
-                         d_xd, d_tk + tofs[c], T, budget, p->Lp, d_xt, d_pk, d_ps, d_pc, d_ds, d_of, d_ov, p->xr_cap);
-      HIP_OK(hipGetLastError());
-      p->merge_launches++;
-    }
-    if (nmulti) {
-      hipLaunchKernelGGL(k_xfinal<XDesc>, dim3((unsigned)nmulti), dim3(256), xf_lds_bytes(p->Lp, p->xf_stage), sw, s, a,
-                         d_xd, d_xt, d_pk, d_ps, d_pc, d_ds, d_of, p->d_dlast, p->Lp, p->xf_stage, maxdiff, p->d_stats);
-      HIP_OK(hipGetLastError());
-      p->merge_launches++;
-    }
-    if ((int64_t)nx > nmulti) {
-      hipLaunchKernelGGL(k_xfin1, dim3((unsigned)((int64_t)nx - nmulti)), dim3(64), xf1_lds_bytes(p->Lp), sw, s, a, d_xd,
-                         (int)nmulti, d_pk, d_ps, d_pc, d_ds, d_of, p->d_dlast, p->Lp, maxdiff, p->d_stats);
-      HIP_OK(hipGetLastError());
-      p->merge_launches++;
-    }
-    if (!a.unit && !a.mc) kst_end(p, 5, sw, p->kst_pend_bytes[5]);
   }
   sub_lap(p, 3, tsub);  // range planning: launches
   // deferred completion (no partitioned or HBM-table source in this call: those plan on the host
@@ -1655,8 +1711,8 @@ static int run_xhubs_list(ppr_plan* p, const IterArgs& a, const std::vector<int3
     defer->depth = depth;
     defer->o_ov = o_ov;
     defer->src = &src; defer->cand = &cand; defer->deg = &deg; defer->dest = &dest;
-    defer->xv.resize(nx);
-    for (size_t i = 0; i < nx; i++) defer->xv[i] = xd[i].v;
+    defer->xv = P.xv;
+    defer->xvp = nullptr;
     return PPR_OK;
   }
   // partitioned sources beside them
@@ -1736,7 +1792,7 @@ static int xhubs_finish(ppr_plan* p, const IterArgs& a, XhDefer& df, unsigned lo
   std::vector<int32_t> rsrc, rcand, rdeg;
   std::vector<int64_t> rdest;
   for (int32_t d : od) {
-    const int32_t v = df.xv[(size_t)d];
+    const int32_t v = (df.xvp ? *df.xvp : df.xv)[(size_t)d];
     auto it = std::lower_bound(idx.begin(), idx.end(), std::make_pair(v, (int32_t)-1));
     if (it == idx.end() || it->first != v) return PPR_ERR_HIP;
     const size_t i = (size_t)it->second;
@@ -1754,7 +1810,7 @@ static int xhubs_finish(ppr_plan* p, const IterArgs& a, XhDefer& df, unsigned lo
 // stream_sv2 (largest first), multi-slice sources by k_svA -> k_svB -> k_svF on stream_sv. The
 // launches are asynchronous; sieve_collect waits and returns the sources handed back.
 struct SvRun {
-  std::vector<int32_t> pos;  // index into the caller's source list of each descriptor
+  const SvPlan* plan = nullptr;  // (pos: index into the caller's source list of each descriptor)
   size_t o_ovl = 0;          // offset of the overflow list in d_sv
   size_t o_os = 0;           // ... and of the small class's first overflows (redone on the device)
   size_t o_om = 0;           // ... and of the mid class's (redone on the device, large geometry)
@@ -1769,16 +1825,17 @@ struct SvRun {
   bool live = false;
 };
 
-static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_t>& src,
-                        const std::vector<int32_t>& cand, const std::vector<int32_t>& deg, unsigned long long* maxdiff,
-                        SvRun& run) {
+// The planning half: order, class ends, descriptors and tasks of the sieve for `src`, uploaded to
+// P.d_up (d_sv, or with `rec` the record's own buffer) on stream_sv3. Depends on the candidate
+// counts and degrees only.
+static int sieve_plan(ppr_plan* p, const std::vector<int32_t>& src, const std::vector<int32_t>& cand,
+                      const std::vector<int32_t>& deg, SvPlan& P, XhRec* rec) {
   const size_t n = src.size();
-  run.live = false;
+  P.n = n;
   if (!n) return PPR_OK;
   auto tsub = std::chrono::steady_clock::now();
-  DevGraph g{p->d_rp, p->d_colx, p->n};
-  const DevSlab s = dev_slab(p);
   const int Lp = p->Lp;
+  std::vector<int32_t>& pos = P.pos;
   // descriptor order: multi-slice sources first (descriptors [0, nm)), then the one-slice ones by
   // size class (large, mid, small), each by candidates descending in eighth-octave steps (largest
   // first keeps the tail short). A counting sort: the host plans hundreds of thousands of sources
@@ -1797,8 +1854,8 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   for (int k = 0; k < NKEY; k++) cnt[k + 1] += cnt[k];
   const size_t nm = cnt[256], nx = n;
   size_t cls_end[3] = {cnt[512], cnt[768], cnt[NKEY]};  // one-slice class ends (descriptor indices)
-  run.pos.resize(nx);
-  for (size_t i = 0; i < n; i++) run.pos[cnt[key[i]]++] = (int32_t)i;
+  pos.resize(nx);
+  for (size_t i = 0; i < n; i++) pos[cnt[key[i]]++] = (int32_t)i;
   // SURVEY s8d bytes of a sieved source: row pointer, its successors' ids and lengths, their rows,
   // its own old row (full: L) and the new one, the length
   auto sv_algo_bytes = [&](size_t i) {
@@ -1809,7 +1866,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   std::vector<SvTask> tasks;
   int64_t tg_total = 0;
   for (size_t k = 0; k < nm; k++) {
-    const size_t i = (size_t)run.pos[k];
+    const size_t i = (size_t)pos[k];
     SvDesc& d = desc[k];
     d = SvDesc{};
     d.v = src[i];
@@ -1856,22 +1913,69 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
   { int r = ensure_pinned(&p->h_sv_pin, &p->h_sv_bytes, up); if (r) return r; }
   unsigned char* hb = (unsigned char*)p->h_sv_pin;
   int32_t* hv = (int32_t*)(hb + o_v);
-  for (size_t k = 0; k < nx; k++) hv[k] = src[(size_t)run.pos[k]];
+  for (size_t k = 0; k < nx; k++) hv[k] = src[(size_t)pos[k]];
   if (nm) std::memcpy(hb + o_d, desc.data(), sizeof(SvDesc) * nm);
   if (nt) std::memcpy(hb + o_t, tasks.data(), sizeof(SvTask) * nt);
-  unsigned char* b = p->d_sv;
-  hipStream_t s1 = p->stream_sv, s2 = p->stream_sv2, s3 = p->stream_sv3;
-  // descriptors up and the zeroed region cleared on the mid class's stream (the plan stream: idle
-  // once the classification is read), the other sieve streams wait for it
+  P.nm = nm; P.nt = nt;
+  for (int c = 0; c < 3; c++) P.cls_end[c] = cls_end[c];
+  P.o_v = o_v; P.o_d = o_d; P.o_t = o_t; P.up = up; P.o_sk = o_sk; P.o_sv = o_sv; P.o_z = o_z; P.o_ov = o_ov;
+  P.o_os = o_os; P.o_om = o_om; P.o_ol = o_ol; P.o_sn = o_sn; P.o_cn = o_cn; P.o_of = o_of; P.o_mk = o_mk;
+  P.o_sd = o_sd; P.o_pt = o_pt; P.o_gs = o_gs; P.o_gk = o_gk; P.o_ga = o_ga; P.o_gb = o_gb; P.total = total;
+  {
+    size_t c0 = nm;
+    for (int c = 0; c < 3; c++) {
+      double bytes = 0.0;
+      for (size_t k = c0; k < cls_end[c]; k++) bytes += sv_algo_bytes((size_t)pos[k]);
+      c0 = cls_end[c];
+      P.bytes[c] = bytes;
+    }
+    double bytes = 0.0;
+    for (size_t k = 0; k < nm; k++) bytes += sv_algo_bytes((size_t)pos[k]);
+    P.bytes[3] = bytes;
+  }
+  P.d_up = p->d_sv;
+  if (rec) {  // the record keeps its descriptors in a buffer of its own
+    int r = ensure_dev(&rec->d_sv_up, &rec->sv_up_bytes, up + 256);
+    if (r) return r;
+    P.d_up = rec->d_sv_up;
+  }
+  // descriptors up on the mid class's stream (the plan stream: idle once the classification is read)
   sub_lap(p, 5, tsub);  // sieve planning: descriptors + staging
-  HIP_OK(hipMemcpyAsync(b, hb, up, hipMemcpyHostToDevice, s3));
+  HIP_OK(hipMemcpyAsync(P.d_up, hb, up, hipMemcpyHostToDevice, p->stream_sv3));
+  return PPR_OK;
+}
+
+// The launching half: the sieve of plan P queued on its streams -- one-slice sources by k_sv1 on
+// stream_sv2 / stream_sv3 (largest first), multi-slice sources by k_svA -> k_svB -> k_svF on
+// stream_sv -- with the work areas of d_sv zeroed first and the retry grids taken from the
+// partition's overflow history as it stands now. A replayed update runs only this.
+static int sieve_queue(ppr_plan* p, const IterArgs& a, const SvPlan& P, unsigned long long* maxdiff, SvRun& run) {
+  run.live = false;
+  run.plan = &P;
+  if (!P.n) return PPR_OK;
+  auto tsub = std::chrono::steady_clock::now();
+  DevGraph g{p->d_rp, p->d_colx, p->n};
+  const DevSlab s = dev_slab(p);
+  const int Lp = p->Lp;
+  const size_t nm = P.nm, nt = P.nt, nx = P.n;
+  const size_t* cls_end = P.cls_end;
+  const size_t o_v = P.o_v, o_d = P.o_d, o_t = P.o_t, o_sk = P.o_sk, o_sv = P.o_sv, o_z = P.o_z, o_ov = P.o_ov,
+               o_os = P.o_os, o_om = P.o_om, o_ol = P.o_ol, o_sn = P.o_sn, o_cn = P.o_cn, o_of = P.o_of,
+               o_mk = P.o_mk, o_sd = P.o_sd, o_pt = P.o_pt, o_gs = P.o_gs, o_gk = P.o_gk, o_ga = P.o_ga,
+               o_gb = P.o_gb, total = P.total;
+  { int r = ensure_dev(&p->d_sv, &p->sv_bytes, total); if (r) return r; }
+  unsigned char* b = p->d_sv;
+  const unsigned char* bu = P.d_up;
+  hipStream_t s1 = p->stream_sv, s2 = p->stream_sv2, s3 = p->stream_sv3;
+  // the zeroed region cleared on the mid class's stream behind the descriptors' upload, the other
+  // sieve streams wait for it
   HIP_OK(hipMemsetAsync(b + o_z, 0, total - o_z, s3));
   HIP_OK(hipEventRecord(p->ev_sv, s3));
   if (s1 != s3) HIP_OK(hipStreamWaitEvent(s1, p->ev_sv, 0));
   if (s2 != s3) HIP_OK(hipStreamWaitEvent(s2, p->ev_sv, 0));
-  const int32_t* d_v = (const int32_t*)(b + o_v);
-  const SvDesc* d_d = (const SvDesc*)(b + o_d);
-  const SvTask* d_t = (const SvTask*)(b + o_t);
+  const int32_t* d_v = (const int32_t*)(bu + o_v);
+  const SvDesc* d_d = (const SvDesc*)(bu + o_d);
+  const SvTask* d_t = (const SvTask*)(bu + o_t);
   int32_t* d_ov = (int32_t*)(b + o_ov);
   int32_t* d_os = (int32_t*)(b + o_os);
   int32_t* d_om = (int32_t*)(b + o_om);
@@ -1917,8 +2021,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
     for (int c = 0; c < 3; c++) {
       const size_t cnt_c = cls_end[c] - c0;
       const int d0 = (int)c0;
-      double bytes = 0.0;
-      for (size_t k = c0; k < cls_end[c]; k++) bytes += sv_algo_bytes((size_t)run.pos[k]);
+      const double bytes = P.bytes[c];
       c0 = cls_end[c];
       if (!cnt_c) continue;
       const SvGeom G = geo[c];
@@ -1969,8 +2072,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
     }
   }
   if (nm) {
-    double bytes = 0.0;
-    for (size_t k = 0; k < nm; k++) bytes += sv_algo_bytes((size_t)run.pos[k]);
+    const double bytes = P.bytes[3];
     kst_begin(p, 4, s1);
     // the chain, and (re-seeding on) once more for the descriptors whose first attempt overflowed:
     // k_svS marks them and writes their seeds, every other block of the second chain leaves at once
@@ -2013,7 +2115,7 @@ static int sieve_launch(ppr_plan* p, const IterArgs& a, const std::vector<int32_
 }
 
 // wait for the sieve, append the sources it handed back (table overflows) to `back`, as indices
-// into the list sieve_launch was given
+// into the list sieve_plan was given
 static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
   if (!run.live) return PPR_OK;
   run.live = false;
@@ -2055,7 +2157,7 @@ static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
   std::vector<int32_t> od(novf);
   HIP_OK(hipMemcpyAsync(od.data(), p->d_sv + run.o_ovl + 4, 4 * (size_t)novf, hipMemcpyDeviceToHost, p->stream_sv));
   HIP_OK(hipStreamSynchronize(p->stream_sv));
-  for (int32_t d : od) back.push_back(run.pos[(size_t)d]);
+  for (int32_t d : od) back.push_back(run.plan->pos[(size_t)d]);
   p->sv_redo += novf;
   return PPR_OK;
 }
@@ -2065,8 +2167,15 @@ static int sieve_collect(ppr_plan* p, SvRun& run, std::vector<int32_t>& back) {
 // row lengths gathered on the device; sources with a full current row go through the sieve
 // (merge_sv.h), the others -- and any the sieve hands back -- through the range / partition
 // engines with the distinct-key estimate planned on the host
-static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int64_t count, unsigned long long* maxdiff) {
+// `R` (an update that records or replays, run_merge_impl): this call's slot of the partition's
+// recorded plan. With `replay` and a live record of the same count, the gather, the split and both
+// plannings are skipped and only the launching halves run; otherwise the call plans
+// as always and leaves its plan in R.
+static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int64_t count, unsigned long long* maxdiff,
+                     XhRec* R = nullptr, bool replay = false) {
   if (count <= 0) return PPR_OK;
+  replay = replay && R && R->live && R->count == count;
+  if (R && !replay) R->live = false;
   auto now = [] { return std::chrono::steady_clock::now(); };
   double lapv[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   auto lap = [&](int k, std::chrono::steady_clock::time_point& t) {
@@ -2095,34 +2204,41 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   } laplog{p, a, lapv, t_in};
   hipStream_t st = p->stream;
   const size_t nh = (size_t)count;
-  {
-    size_t capb = p->h_hub_cap * 12;
-    void* ptr = p->h_hub_pin;
-    int r = ensure_pinned(&ptr, &capb, 20 * nh);
-    if (r) return r;
-    p->h_hub_pin = (int32_t*)ptr;
-    p->h_hub_cap = capb / 12;
+  std::vector<int32_t>& hcopy = R ? R->h : p->xhs.h;  // (the pinned buffer is restaged by later calls)
+  if (!replay) {
+    {
+      size_t capb = p->h_hub_cap * 12;
+      void* ptr = p->h_hub_pin;
+      int r = ensure_pinned(&ptr, &capb, 20 * nh);
+      if (r) return r;
+      p->h_hub_pin = (int32_t*)ptr;
+      p->h_hub_cap = capb / 12;
+    }
+    if (4 * nh > (size_t)p->n) { int r = ensure_dev((unsigned char**)&p->d_gath, &p->gath_bytes, 16 * nh); if (r) return r; }
+    int32_t* d_g = 4 * nh > (size_t)p->n ? p->d_gath : p->d_ovf;
+    int32_t* hp = p->h_hub_pin;
+    HIP_OK(hipMemcpyAsync(hp, d_list, 4 * nh, hipMemcpyDeviceToHost, st));
+    hipLaunchKernelGGL(k_gather_sv, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, st, d_list, (int64_t)nh,
+                       p->d_cand, p->d_rp, (const int32_t*)p->d_dlast, dev_slab(p), a, d_g);
+    HIP_OK(hipGetLastError());
+    HIP_OK(hipMemcpyAsync(hp + nh, d_g, 16 * nh, hipMemcpyDeviceToHost, st));
+    HIP_OK(hipStreamSynchronize(st));
+    hcopy.assign(hp, hp + 5 * nh);
   }
-  if (4 * nh > (size_t)p->n) { int r = ensure_dev((unsigned char**)&p->d_gath, &p->gath_bytes, 16 * nh); if (r) return r; }
-  int32_t* d_g = 4 * nh > (size_t)p->n ? p->d_gath : p->d_ovf;
-  int32_t* h = p->h_hub_pin;
-  HIP_OK(hipMemcpyAsync(h, d_list, 4 * nh, hipMemcpyDeviceToHost, st));
-  hipLaunchKernelGGL(k_gather_sv, dim3((unsigned)((nh + 255) / 256)), dim3(256), 0, st, d_list, (int64_t)nh,
-                     p->d_cand, p->d_rp, (const int32_t*)p->d_dlast, dev_slab(p), a, d_g);
-  HIP_OK(hipGetLastError());
-  HIP_OK(hipMemcpyAsync(h + nh, d_g, 16 * nh, hipMemcpyDeviceToHost, st));
-  HIP_OK(hipStreamSynchronize(st));
-  std::vector<int32_t>& hcopy = p->xhs.h;  // (the pinned buffer is restaged by later calls)
-  hcopy.assign(h, h + 5 * nh);
-  h = hcopy.data();
+  // sources | candidate counts | degrees | last distinct counts | current row lengths (a replayed
+  // call: as recorded; the distinct counts only feed the estimate of a hand-back's redo)
+  const int32_t* h = hcopy.data();
   lap(0, tl);  // gather + copy back
   const bool sieve = p->sv_enabled && a.xs && !a.unit && !a.mc && p->hot_n == 0;
-  std::vector<int32_t>& src = p->xhs.src; std::vector<int32_t>& cand = p->xhs.cand;
-  std::vector<int32_t>& deg = p->xhs.deg; std::vector<int32_t>& ssrc = p->xhs.ssrc;
-  std::vector<int32_t>& scand = p->xhs.scand; std::vector<int32_t>& sdeg = p->xhs.sdeg;
-  std::vector<int32_t>& sidx = p->xhs.sidx;
-  std::vector<int64_t>& dest = p->xhs.dest;
-  src.clear(); cand.clear(); deg.clear(); ssrc.clear(); scand.clear(); sdeg.clear(); sidx.clear(); dest.clear();
+  // (a recording call plans straight into the record's lists)
+  std::vector<int32_t>& src = R ? R->src : p->xhs.src; std::vector<int32_t>& cand = R ? R->cand : p->xhs.cand;
+  std::vector<int32_t>& deg = R ? R->deg : p->xhs.deg; std::vector<int32_t>& ssrc = R ? R->ssrc : p->xhs.ssrc;
+  std::vector<int32_t>& scand = R ? R->scand : p->xhs.scand; std::vector<int32_t>& sdeg = R ? R->sdeg : p->xhs.sdeg;
+  std::vector<int32_t>& sidx = R ? R->sidx : p->xhs.sidx;
+  std::vector<int64_t>& dest = R ? R->dest : p->xhs.dest;
+  if (!replay) {
+    src.clear(); cand.clear(); deg.clear(); ssrc.clear(); scand.clear(); sdeg.clear(); sidx.clear(); dest.clear();
+  }
   // distinct keys expected: the last merge's count (rows change little between updates) plus a
   // margin, else (first merge) 60 % of the candidates; never more than the candidates + 1
   auto estimate = [&](size_t i) {
@@ -2151,7 +2267,7 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
     if (c > p->sv_slice) return false;
     return c >= p->sv_mid ? short_large : c >= p->sv_small ? short_mid : p->sv_redo_mid;
   };
-  for (size_t i = 0; i < nh; i++) {
+  for (size_t i = 0; i < nh && !replay; i++) {
     const int32_t c = h[nh + i];
     if (sieve && c >= p->sv_min && c < (1 << 30) &&
         (h[4 * nh + i] == (int32_t)p->L || (seedless && short_ok(c)))) {
@@ -2168,21 +2284,46 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   }
   lap(1, tl);  // classification
   SvRun run;
+  SvPlan svl;
+  SvPlan& svp = R ? R->sv : svl;
   const int64_t rl0 = p->sv_retry_launched, rp0 = p->sv_retry_skipped;  // (PPR_SV_LOG: this call's)
+  // the range engines of a replayed call: the recorded plan queued, collected by xhubs_finish
+  auto xr_replay = [&](XhDefer& d) -> int {
+    if (src.empty()) return PPR_OK;
+    int r = xr_queue(p, a, R->xr, maxdiff);
+    if (r) return r;
+    d.live = true;
+    d.depth = 0;
+    d.o_ov = R->xr.o_ov;
+    d.src = &src; d.cand = &cand; d.deg = &deg; d.dest = &dest;
+    d.xvp = &R->xr.xv;
+    return PPR_OK;
+  };
+  auto sieve_go = [&]() -> int {
+    if (ssrc.empty()) return PPR_OK;
+    if (!replay) { int r = sieve_plan(p, ssrc, scand, sdeg, svp, R); if (r) return r; }
+    return sieve_queue(p, a, svp, maxdiff, run);
+  };
   // the larger of the two host plannings goes second: when the range engines take more sources
   // than the sieve (the big partition's iterations: ~258 K mid-sized sources at RMAT-22), they are
   // planned and queued first and collected after the sieve's launches (PPR_XH_FIRST=0: sieve first)
   XhDefer df;
   df.want = p->xh_first && src.size() > ssrc.size();
-  if (df.want) { int r = run_xhubs_list(p, a, src, cand, deg, dest, maxdiff, 0, &df); if (r) return r; }
-  if (!ssrc.empty()) { int r = sieve_launch(p, a, ssrc, scand, sdeg, maxdiff, run); if (r) return r; }
+  if (df.want) { int r = replay ? xr_replay(df) : run_xhubs_list(p, a, src, cand, deg, dest, maxdiff, 0, &df, R); if (r) return r; }
+  { int r = sieve_go(); if (r) return r; }
   lap(2, tl);  // sieve planning + launches
-  if (df.want) {
+  if (!df.want && replay) { int r = xr_replay(df); if (r) return r; }
+  if (df.want || replay) {
     int r = xhubs_finish(p, a, df, maxdiff);
     if (r) return r;
   } else if (!src.empty()) {
-    int r = run_xhubs_list(p, a, src, cand, deg, dest, maxdiff, 0);
+    int r = run_xhubs_list(p, a, src, cand, deg, dest, maxdiff, 0, nullptr, R);
     if (r) return r;
+  }
+  // the call's plan is complete (every source sieved or ranged: no partitioned or HBM-table source)
+  if (R && !replay) {
+    R->count = count;
+    R->live = src.empty() || R->xr.simple;
   }
   lap(3, tl);  // range / partition engines (their syncs included)
   std::vector<int32_t>& back = p->xhs.back;
@@ -2194,10 +2335,10 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
   if (getenv("PPR_SV_LOG")) {
     // hand-backs by class (sources, and the candidates they carry): the large, mid and small one-slice
     // classes (the small class after its device redo) and the multi-slice sources
-    // (a source's class from its descriptor index: run.pos maps descriptors to sources, inverted here)
+    // (a source's class from its descriptor index: the plan's pos maps descriptors to sources, inverted here)
     long long hn[4] = {0, 0, 0, 0}, hc[4] = {0, 0, 0, 0}, sc = 0;
     std::vector<int32_t> desc_of(ssrc.size(), 0);
-    for (size_t d = 0; d < run.pos.size(); d++) desc_of[(size_t)run.pos[d]] = (int32_t)d;
+    for (size_t d = 0; d < svp.pos.size() && !ssrc.empty(); d++) desc_of[(size_t)svp.pos[d]] = (int32_t)d;
     for (size_t k = 0; k < back.size(); k++) {
       int c = 0;
       while (c < 3 && (size_t)desc_of[(size_t)back[k]] >= run.cls_end[c]) c++;
@@ -2215,17 +2356,19 @@ static int run_xhubs(ppr_plan* p, const IterArgs& a, const int32_t* d_list, int6
             (long long)(p->sv_seedless_done - sd0));
   }
   if (back.empty()) return PPR_OK;
-  // handed back: the range / partition engines, with the usual estimate
-  src.clear(); cand.clear(); deg.clear(); dest.clear();
+  // handed back: the range / partition engines, with the usual estimate (lists of their own: the
+  // call's lists may be a recorded plan's)
+  std::vector<int32_t> bsrc, bcand, bdeg;
+  std::vector<int64_t> bdest;
   for (int32_t k : back) {
     const size_t i = (size_t)sidx[(size_t)k];
-    src.push_back(h[i]);
-    cand.push_back(h[nh + i]);
-    deg.push_back(h[2 * nh + i]);
-    dest.push_back(estimate(i));
+    bsrc.push_back(h[i]);
+    bcand.push_back(h[nh + i]);
+    bdeg.push_back(h[2 * nh + i]);
+    bdest.push_back(estimate(i));
   }
   lap(5, tl);  // hand-back planning
-  const int r = run_xhubs_list(p, a, src, cand, deg, dest, maxdiff, 0);
+  const int r = run_xhubs_list(p, a, bsrc, bcand, bdeg, bdest, maxdiff, 0);
   lap(6, tl);  // hand-backs merged
   return r;
 }
@@ -2243,16 +2386,40 @@ int run_merge(ppr_plan* p, const IterArgs& a, const int32_t* list, int64_t count
     HIP_OK(hipEventRecord(p->ev_wave, p->stream_wave));
     HIP_OK(hipStreamWaitEvent(p->stream, p->ev_wave, 0));
   }
+  // the recorded plans' clock (replay_rule.h) is read once per update, here at its end, in the same
+  // host sync as the wave tier's overflow count; a redo below is read once more
+  const bool clock = !rc && a.xs && !a.mc;
+  unsigned long long lenchg = 0;
+  constexpr size_t NSH = (size_t)PPR_LENCHG_SHARDS * PPR_LENCHG_STRIDE;
+  if (clock) p->rp_shards.resize(NSH);
+  auto sum_shards = [&] {
+    lenchg = 0;
+    for (int k = 0; k < PPR_LENCHG_SHARDS; k++) lenchg += p->rp_shards[(size_t)k * PPR_LENCHG_STRIDE];
+  };
   if (!rc && p->wave_x_launched) {
     // exact wave tier: sources whose table ran out (only with PPR_WAVE_TDIV: the tables hold 4/3 of
     // the tier's candidate cap) wrote no row; the workgroup engines merge them again
     int32_t nw = 0;
     HIP_OK(hipMemcpyAsync(&nw, p->d_wovl, 4, hipMemcpyDeviceToHost, p->stream));
+    if (clock) HIP_OK(hipMemcpyAsync(p->rp_shards.data(), p->d_stats + PPR_STAT_LENCHG, 8 * NSH, hipMemcpyDeviceToHost, p->stream));
     HIP_OK(hipStreamSynchronize(p->stream));
     if (nw) {
       p->wave_redo += nw;
       rc = run_xhubs(p, a, p->d_wovl + 1, nw, maxdiff);
+      if (!rc && clock) {
+        HIP_OK(hipMemcpyAsync(p->rp_shards.data(), p->d_stats + PPR_STAT_LENCHG, 8 * NSH, hipMemcpyDeviceToHost, p->stream));
+        HIP_OK(hipStreamSynchronize(p->stream));
+      }
     }
+  } else if (clock) {
+    HIP_OK(hipMemcpyAsync(p->rp_shards.data(), p->d_stats + PPR_STAT_LENCHG, 8 * NSH, hipMemcpyDeviceToHost, p->stream));
+    HIP_OK(hipStreamSynchronize(p->stream));
+  }
+  if (clock && !rc) {
+    sum_shards();
+    if (p->rp_clock.valid && !a.unit) p->rp_len_changes += (int64_t)(lenchg - p->rp_clock.len_changes);
+    p->rp_clock.len_changes = lenchg;
+    p->rp_clock.valid = true;
   }
   if (rc || a.mc) return rc;
   HIP_OK(hipEventRecord(p->ev_m1, p->stream));
@@ -2356,25 +2523,77 @@ static int run_merge_impl(ppr_plan* p, const IterArgs& a, const int32_t* list, i
     p->h_hub_pin = (int32_t*)ptr;
     p->h_hub_cap = capb / 12;
   }
-reclassify:
-  HIP_OK(hipMemsetAsync(p->d_tier_cnt, 0, sizeof(uint32_t) * (NLISTS + 2), st));
-  const int cls_pw = count <= CLS_SMALL ? 1 : CLS_PER_WAVE;
-  const int64_t cls_pb = (int64_t)cls_pw * WAVES_PER_BLOCK;
-  const int64_t nb = (count + cls_pb - 1) / cls_pb;
-  hipLaunchKernelGGL(k_classify, dim3((unsigned)nb), dim3(256), 0, st, g, s, a, list, count,
-                     p->d_tier_cap, p->d_tier_lists, p->d_tier_cnt, p->n, p->d_cand, p->d_stats, p->d_big, cls_pw,
-                     (p->wave_by_d && a.xs && !a.unit && !a.mc) ? (const int32_t*)p->d_dlast : nullptr);
-  HIP_OK(hipGetLastError());
-  if (!a.unit && p->max_deg > CLS_BIG_DEG) {
-    // grid-stride over the long-list sources, at most one block per listed source
-    hipLaunchKernelGGL(k_classify_big, dim3((unsigned)std::min<int64_t>(256, count)), dim3(CLS_BIG_THREADS), 0, st, g,
-                       s, a, p->d_tier_cap,
-                       p->d_tier_lists, p->d_tier_cnt, p->n, p->d_cand, p->d_stats, p->d_big,
-                       (p->wave_by_d && a.xs && !a.unit && !a.mc) ? (const int32_t*)p->d_dlast : nullptr);
+  // Exact-sum GRank updates of a range of a partition's active list record their plan, and replay
+  // the one recorded two updates earlier while no row has changed its length since (replay_rule.h,
+  // DESIGN.md s3.9). A recording update classifies into tier lists of the partition's own (the
+  // other partition's classification overwrites d_tier_lists) and into statistics of its own.
+  ReplayRec* RR = nullptr;
+  int64_t rp_begin = 0;
+  bool replayed = false;
+  {
+    const int part = a.active == 1 ? 1 : 0;
+    const ReplayKnobs kn = replay_knobs(p);
+    const bool grank_update = a.xs && !a.unit && !a.mc && (a.active == 0 || a.active == 1);
+    const bool in_list = grank_update && list >= p->d_act[part] && list + count <= p->d_act[part] + p->nact[part];
+    // (the updates must come iteration after iteration, each over its whole list: replay_rule.h)
+    if (grank_update) replay_begin_update(p->rp_clock, a.iter, count, p->nact[part ^ 1], in_list);
+    if (in_list && replay_allowed(kn)) {
+      RR = &p->rp[part];
+      rp_begin = (int64_t)(list - p->d_act[part]);
+      replayed = replay_valid(RR->stamp, p->rp_clock, part, rp_begin, rp_begin + count, kn);
+      if (!replayed) {
+        if (RR->stamp.live) p->rp_dropped++;
+        RR->stamp.live = false;
+        for (XhRec& x : RR->xh) x.live = false;
+        int rc = ensure_dev((unsigned char**)&RR->d_tl, &RR->tl_bytes, 4 * (size_t)NLISTS * (size_t)count);
+        if (rc) return rc;
+        RR->tl_cap = count;
+        if (!RR->d_st) HIP_OK(hipMalloc((void**)&RR->d_st, 8 * 4));
+        HIP_OK(hipMemsetAsync(RR->d_st, 0, 8 * 4, st));
+      }
+    }
   }
-  HIP_OK(hipGetLastError());
+  int32_t* const tlists = RR ? RR->d_tl : p->d_tier_lists;  // tier t: tlists + t * tcap
+  const int64_t tcap = RR ? RR->tl_cap : p->n;
+  unsigned long long* const cls_stats = RR ? RR->d_st : p->d_stats;
   uint32_t cnt[NLISTS + 1];
-  if (fused) {
+reclassify:
+  if (!replayed) {
+    HIP_OK(hipMemsetAsync(p->d_tier_cnt, 0, sizeof(uint32_t) * (NLISTS + 2), st));
+    const int cls_pw = count <= CLS_SMALL ? 1 : CLS_PER_WAVE;
+    const int64_t cls_pb = (int64_t)cls_pw * WAVES_PER_BLOCK;
+    const int64_t nb = (count + cls_pb - 1) / cls_pb;
+    hipLaunchKernelGGL(k_classify, dim3((unsigned)nb), dim3(256), 0, st, g, s, a, list, count,
+                       p->d_tier_cap, tlists, p->d_tier_cnt, tcap, p->d_cand, cls_stats, p->d_big, cls_pw,
+                       (p->wave_by_d && a.xs && !a.unit && !a.mc) ? (const int32_t*)p->d_dlast : nullptr);
+    HIP_OK(hipGetLastError());
+    if (!a.unit && p->max_deg > CLS_BIG_DEG) {
+      // grid-stride over the long-list sources, at most one block per listed source
+      hipLaunchKernelGGL(k_classify_big, dim3((unsigned)std::min<int64_t>(256, count)), dim3(CLS_BIG_THREADS), 0, st, g,
+                         s, a, p->d_tier_cap,
+                         tlists, p->d_tier_cnt, tcap, p->d_cand, cls_stats, p->d_big,
+                         (p->wave_by_d && a.xs && !a.unit && !a.mc) ? (const int32_t*)p->d_dlast : nullptr);
+    }
+    HIP_OK(hipGetLastError());
+  }
+  // the list's share of the run's statistics, as classified now or when the plan was recorded
+  if (RR && a.stats) {
+    hipLaunchKernelGGL(k_stats_add, dim3(1), dim3(64), 0, st, p->d_stats, (const unsigned long long*)RR->d_st);
+    HIP_OK(hipGetLastError());
+  }
+  if (replayed) {
+    std::memcpy(cnt, RR->cnt, sizeof(cnt));
+    p->rp_replayed++;
+    // no host sync follows: the other streams start behind what the plan stream still holds
+    if (!p->ev_rp) HIP_OK(hipEventCreateWithFlags(&p->ev_rp, hipEventDisableTiming));
+    HIP_OK(hipEventRecord(p->ev_rp, st));
+    hipStream_t side[5] = {p->stream_wave, p->stream3, p->stream_sv, p->stream_sv2, p->stream_sv3};
+    for (int i = 0; i < 5; i++) {
+      bool seen = !side[i] || side[i] == st;
+      for (int j = 0; j < i; j++) seen = seen || side[j] == side[i];
+      if (!seen) HIP_OK(hipStreamWaitEvent(side[i], p->ev_rp, 0));
+    }
+  } else if (fused) {
     static_assert(NLISTS + 1 < GATHER_HDR, "tier counters and the pending count fit the header");
     hipLaunchKernelGGL(k_gather_cand_deg_dev, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, st,
                        p->d_tier_lists + (int64_t)TIER_BIG * p->n, p->d_tier_cnt, NLISTS + 1, TIER_BIG,
@@ -2396,6 +2615,11 @@ reclassify:
   } else {
     HIP_OK(hipMemcpyAsync(cnt, p->d_tier_cnt, sizeof(cnt), hipMemcpyDeviceToHost, st));
     HIP_OK(hipStreamSynchronize(st));
+    if (RR) {
+      std::memcpy(RR->cnt, cnt, sizeof(cnt));
+      RR->stamp = replay_stamp(p->rp_clock, a.active == 1 ? 1 : 0, rp_begin, rp_begin + count);
+      if (RR->stamp.live) p->rp_recorded++;
+    }
   }
   // the classification is complete (host sync): the wave tiers need no event to start on their stream
   hipStream_t sw = p->stream_wave ? p->stream_wave : st;
@@ -2451,7 +2675,7 @@ reclassify:
       // the tables end after their compaction: the row in k_wfin (merge_xs.h WList)
       const WList wl = wls[t];
       const bool split = wl.cap != 0;
-      const int32_t* tl = p->d_tier_lists + (int64_t)t * p->n;
+      const int32_t* tl = tlists + (int64_t)t * tcap;
       const size_t wlds = split ? lds_wave_bytes_xs(Tw) : lds_wave_bytes_x(Tw, p->Lp);
       const int64_t step = split ? wchunk : (int64_t)cnt[t];
       for (int64_t c0 = 0; c0 < (int64_t)cnt[t]; c0 += step) {
@@ -2493,10 +2717,16 @@ reclassify:
     // wave kernel) goes through the range / bucket workgroups -- nothing falls to the chain-order
     // HBM table
     int r = PPR_OK;
+    static_assert(ReplayRec::NCALL == NLISTS, "one recorded run_xhubs call per tier list");
     for (int t = 0; t < NT && !r; t++)
-      if (cnt[t] && !p->tierT[t]) r = run_xhubs(p, a, p->d_tier_lists + (int64_t)t * p->n, cnt[t], maxdiff);
-    if (!r && cnt[TIER_WG]) r = run_xhubs(p, a, p->d_tier_lists + (int64_t)TIER_WG * p->n, cnt[TIER_WG], maxdiff);
-    if (!r && cnt[TIER_BIG]) r = run_xhubs(p, a, p->d_tier_lists + (int64_t)TIER_BIG * p->n, cnt[TIER_BIG], maxdiff);
+      if (cnt[t] && !p->tierT[t])
+        r = run_xhubs(p, a, tlists + (int64_t)t * tcap, cnt[t], maxdiff, RR ? &RR->xh[t] : nullptr, replayed);
+    if (!r && cnt[TIER_WG])
+      r = run_xhubs(p, a, tlists + (int64_t)TIER_WG * tcap, cnt[TIER_WG], maxdiff, RR ? &RR->xh[TIER_WG] : nullptr,
+                    replayed);
+    if (!r && cnt[TIER_BIG])
+      r = run_xhubs(p, a, tlists + (int64_t)TIER_BIG * tcap, cnt[TIER_BIG], maxdiff, RR ? &RR->xh[TIER_BIG] : nullptr,
+                    replayed);
     return r;
   }
   if (cnt[TIER_WG]) {
@@ -2604,6 +2834,7 @@ extern "C" int ppr_grank_plan_init(ppr_plan* p) {
   // the last merge's count) start over, so a repeated run is a cold call
   if (p->d_dlast) HIP_OK(hipMemsetAsync(p->d_dlast, 0, 4 * (size_t)std::max<int64_t>(1, p->n), p->stream));
   p->sv_hist[0] = p->sv_hist[1] = SvHist{};  // (and the sieve's retry grids from its own overflows only)
+  plan_replay_drop(p);  // (and no recorded merge plan outlives the rows it was planned from)
   IterArgs a = iter_args(p, 0, true);
   int rc = init_dangling(p, p->d_all + p->n_nd, p->n - p->n_nd);
   if (rc) return rc;
@@ -2908,6 +3139,7 @@ static int xpack_nodes(ppr_plan* p, int nxt, const int32_t* list, int64_t cnt, u
 }
 
 static int xunpack_nodes(ppr_plan* p, int nxt, const int32_t* list, int64_t cnt, const unsigned char* buf) {
+  plan_replay_drop(p);  // imported rows bring their own lengths, uncounted (replay_rule.h)
   if (cnt == 0) return PPR_OK;
   hipLaunchKernelGGL(k_xunpack, dim3((unsigned)((cnt + 3) / 4)), dim3(256), 0, p->stream, dev_slab(p), nxt, list, cnt,
                      buf);
@@ -3505,6 +3737,8 @@ static int run_sharded_impl(ppr_plan* p, uint32_t iterations, double tolerance, 
   if (iterations == 0) return PPR_ERR_ITERS;
   if (p->nranks > 1 && !p->comm && !p->lgroup) return PPR_ERR_ARG;
   HIP_OK(hipSetDevice(p->device));
+  p->replay_sharded = true;  // rows arrive by exchange: every update of this plan plans afresh (replay_rule.h)
+  plan_replay_drop(p);
   hipStream_t s = p->stream;
   HIP_OK(hipMemsetAsync(p->d_maxdiff, 0, 8 * (PPR_MAX_ITER_STATS + 1), s));
   HIP_OK(hipMemsetAsync(p->d_stats, 0, 8 * PPR_NSTATS, s));

@@ -130,6 +130,7 @@ extern "C" int ppr_mccp2_plan_walk(ppr_plan* p, uint32_t walks, uint64_t seed, i
   end = std::min<int64_t>(p->mc_nwalk, end);
   if (end <= begin) return PPR_OK;
   HIP_OK(hipSetDevice(p->device));
+  plan_replay_drop(p);  // (the MC kernels write row lengths uncounted: replay_rule.h)
   McArgs m;
   m.R = walks;
   // walks = static_cast<size_t>(static_cast<double>(walks) * damping) (:132)
@@ -157,6 +158,7 @@ extern "C" int ppr_mccp2_plan_combine(ppr_plan* p) {
   if (!p || !p->mc) return PPR_ERR_ARG;
   if (p->n == 0) return PPR_OK;
   HIP_OK(hipSetDevice(p->device));
+  plan_replay_drop(p);  // (the MC kernels write row lengths uncounted: replay_rule.h)
   const DevSlab s = dev_slab(p);
   if (p->mc_ndangling) {
     hipLaunchKernelGGL(k_mc_selfrow, dim3((unsigned)((p->mc_ndangling + 3) / 4)), dim3(256), 0, p->stream, s,

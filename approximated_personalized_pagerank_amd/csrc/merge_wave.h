@@ -187,6 +187,13 @@ __global__ void __launch_bounds__(256) k_stat_written(DevSlab s, IterArgs a, con
   }
 }
 
+// a recorded classification's statistics (candidates, algorithmic bytes, wave-tier bytes: what
+// k_classify adds for the list) added to the run's counters: the recording update classifies into
+// `add`, a replayed one adds the same figures without classifying
+__global__ void k_stats_add(unsigned long long* stats, const unsigned long long* add) {
+  if (threadIdx.x < 3 && add[threadIdx.x]) atomicAdd(&stats[threadIdx.x], add[threadIdx.x]);
+}
+
 // per-wave LDS bytes for table size T and padded width Lp (layout: k_merge_lds below)
 __host__ __device__ constexpr size_t lds_wave_bytes(int T, int Lp) {
   return (size_t)T * 13 + (size_t)Lp * 12 + 1024 + (size_t)Lp * 20;

@@ -11,6 +11,7 @@
 #include "../../include/ppr_hip.h"
 #include "ppr_common.h"
 #include "sv_plan.h"
+#include "replay_rule.h"
 
 using namespace pprk;
 
@@ -31,6 +32,57 @@ inline int pow2_at_least(int64_t x) {
   return p;
 }
 
+
+// ================================================================================================
+// Recorded merge plans: what one exact-sum update of a partition planned, kept so a
+// later update of the same list can queue its kernels without classifying again (replay_rule.h).
+// The planning halves of sieve_launch / run_xhubs_list (grank.hip) fill these, the launching halves
+// read them. Descriptors and tasks sit in a device buffer of the record's own (`d_up`: d_sv and d_xs
+// are shared by both partitions); the work areas every launch zeroes stay in d_sv / d_xs.
+struct SvPlan {
+  std::vector<int32_t> pos;  // index into the caller's source list of each descriptor
+  size_t n = 0, nm = 0, nt = 0;
+  size_t cls_end[3] = {0, 0, 0};  // one-slice class ends (descriptor indices): large, mid, small
+  // d_up: node ids | multi descriptors | tasks;  d_sv: (the same, unused with a buffer of its own) |
+  // one-slice selections | zeroed lists and counters | multi-slice tables (sieve_plan, grank.hip)
+  size_t o_v = 0, o_d = 0, o_t = 0, up = 0, o_sk = 0, o_sv = 0, o_z = 0, o_ov = 0, o_os = 0, o_om = 0, o_ol = 0,
+         o_sn = 0, o_cn = 0, o_of = 0, o_mk = 0, o_sd = 0, o_pt = 0, o_gs = 0, o_gk = 0, o_ga = 0, o_gb = 0, total = 0;
+  double bytes[4] = {0, 0, 0, 0};  // algorithmic bytes of the large, mid, small and multi-slice groups
+  unsigned char* d_up = nullptr;   // where the descriptors are (not owned: the record's buffer or d_sv)
+};
+struct XrPlan {
+  size_t n = 0, nx = 0, nmulti = 0, nxm = 0, ntask = 0;
+  size_t tcount[3] = {0, 0, 0}, tofs[3] = {0, 0, 0};  // k_xr tasks per table class
+  int64_t pt = 0;                                     // list entries of all descriptors
+  size_t o_d = 0, o_t = 0, o_m = 0, up = 0, o_k = 0, o_s = 0, o_z = 0, o_pc = 0, o_ds = 0, o_of = 0, o_ov = 0,
+         o_xt = 0, total = 0;
+  double bytes = 0.0;              // algorithmic bytes of the ranged sources
+  bool simple = false;             // no partitioned and no HBM-table source: the plan is complete
+  std::vector<int32_t> xv;         // source of each descriptor
+  unsigned char* d_up = nullptr;   // descriptors | tasks | k_xm tasks (not owned)
+};
+// one run_xhubs call of a recorded update
+struct XhRec {
+  bool live = false;
+  int64_t count = 0;
+  std::vector<int32_t> h, src, cand, deg, ssrc, scand, sdeg, sidx;
+  std::vector<int64_t> dest;
+  SvPlan sv;
+  XrPlan xr;
+  unsigned char* d_sv_up = nullptr;  // owned: the sieve's and the range engines' descriptor buffers
+  unsigned char* d_xr_up = nullptr;
+  size_t sv_up_bytes = 0, xr_up_bytes = 0;
+};
+struct ReplayRec {
+  static constexpr int NCALL = NT + 2;  // run_xhubs calls of one update: kernel-less wave tiers, TIER_WG, TIER_BIG
+  ReplayStamp stamp;
+  uint32_t cnt[NLISTS + 1] = {};
+  int32_t* d_tl = nullptr;  // owned: the tier lists of this partition's classification, NLISTS x tl_cap
+  int64_t tl_cap = 0;       // entries per tier (the classified count)
+  size_t tl_bytes = 0;
+  unsigned long long* d_st = nullptr;  // owned: what k_classify added to d_stats[0..2] for the list
+  XhRec xh[NCALL];
+};
 
 // ================================================================================================
 // plan
@@ -236,6 +288,14 @@ struct ppr_plan {
     std::vector<uint32_t> svcnt;
   } xhs;
   double xh_sub[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // (PPR_SV_LOG) host planning sub-phases, seconds
+  // recorded merge plans, one per partition (PPR_REPLAY=0: every update plans afresh)
+  bool replay = true;
+  bool replay_sharded = false;        // a communicator or a sharded loop was set up: rows arrive by exchange
+  ReplayRec rp[2];
+  ReplayClock rp_clock;               // the shards of d_stats + PPR_STAT_LENCHG as summed at the end of the last update
+  std::vector<unsigned long long> rp_shards;  // (their host copy)
+  hipEvent_t ev_rp = nullptr;         // a replayed update's side streams start behind the plan stream
+  int64_t rp_recorded = 0, rp_replayed = 0, rp_dropped = 0, rp_len_changes = 0;  // (PPR_TIMING at destroy)
   int xr_cap = 0;                     // PPR_XR_LISTCAP: one-range k_xr sources emit up to this many unselected
                                       // entries for k_xfin1 (set to 2 Lp at plan creation; 0: k_xr selects)
   int wave_cap = 0;                   // (tests) PPR_WAVE_CAP: list entries per split source (>= L; 0: 2 Lp)
@@ -312,6 +372,16 @@ struct ppr_plan {
   int64_t mc_walks = 0;
 };
 
+// Row lengths are about to be written by something that does not count its changes (an init, a row
+// import, an MC run): no recorded plan survives it, and the counter is read again before the next one
+inline void plan_replay_drop(ppr_plan* p) {
+  for (ReplayRec& r : p->rp) {
+    if (r.stamp.live) p->rp_dropped++;
+    r.stamp.live = false;
+  }
+  replay_drop(p->rp_clock);
+}
+
 inline void plan_free(ppr_plan* p) {
   if (!p) return;
   hipFree(p->d_rp); hipFree(p->d_colx); hipFree(p->d_part); hipFree(p->d_ids); hipFree(p->d_sc); hipFree(p->d_rix); hipFree(p->d_rmin);
@@ -355,6 +425,15 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_r); hipFree(p->d_rl); hipFree(p->d_rt);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
+  if (p->ev_rp) hipEventDestroy(p->ev_rp);
+  for (ReplayRec& r : p->rp) {
+    hipFree(r.d_tl); hipFree(r.d_st);
+    for (XhRec& x : r.xh) { hipFree(x.d_sv_up); hipFree(x.d_xr_up); }
+  }
+  if (getenv("PPR_TIMING") && p->xsum && !p->mc)
+    fprintf(stderr, "ppr_timing replay recorded %lld replayed %lld dropped %lld len_changes %lld\n",
+            (long long)p->rp_recorded, (long long)p->rp_replayed, (long long)p->rp_dropped,
+            (long long)p->rp_len_changes);
   if (getenv("PPR_TIMING") && p->sv_sources)
     fprintf(stderr, "ppr_timing sieve_sources %lld sieve_redo %lld sieve_redo_dev %lld sieve_reseed %lld "
             "sieve_reseed_ok %lld\n", (long long)p->sv_sources, (long long)p->sv_redo, (long long)p->sv_redo_dev,

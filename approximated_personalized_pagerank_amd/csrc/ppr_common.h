@@ -24,6 +24,13 @@ constexpr int NLISTS = NT + 2;
 constexpr int MAX_L = 4096;           // widest basket the kernels accept
 constexpr int WAVES_PER_BLOCK = 4;
 constexpr int PPR_NSTATS = 8;         // device counters: candidates, algorithmic bytes, wave-tier bytes
+// ... and behind them the rows a GRank merge stored with a length other than the one they replace:
+// the clock of the recorded merge plans (replay_rule.h). A partition's first updates change nearly
+// every length -- millions of adds, which on one address cost an RMAT-22 job 14 ms -- so the count is
+// kept in PPR_LENCHG_SHARDS words a cache line apart, picked by the source; the host sums them.
+constexpr int PPR_STAT_LENCHG = PPR_NSTATS;  // first shard
+constexpr int PPR_LENCHG_SHARDS = 256, PPR_LENCHG_STRIDE = 16;  // (words: 128 B)
+constexpr int PPR_NSTATS_ALL = PPR_NSTATS + PPR_LENCHG_SHARDS * PPR_LENCHG_STRIDE;
 // PPR_DIAG counters (u64, printed at plan destruction, plan.h): PPR_DIAG_BASE counters, plus as
 // many per shard -- per-wave counters go to a shard picked by block and wave, so hundreds of
 // millions of waves do not serialise on a few addresses (that contention distorted the timings)
@@ -405,6 +412,7 @@ __device__ __forceinline__ void finish_source(int v, int U, KeyAt keyat, ValAt v
   const int nxt = cur ^ 1;
   fs_lap(a, dg, 0, tl);
   double d1;
+  int oldlen = olen;  // length of the row this one replaces
   if (reg) {
     const int l = lane_id();
     const int k0 = l < cnt ? rk[l] : EMPTY, k1 = l + WAVE < cnt ? rk[l + WAVE] : EMPTY;
@@ -418,6 +426,7 @@ __device__ __forceinline__ void finish_source(int v, int U, KeyAt keyat, ValAt v
     fs_lap(a, dg, 1, tl);
     const int64_t ro = s.row(cur, v);
     const int olen2 = s.len[s.lrow(cur, v)];
+    oldlen = olen2;
     d1 = row_norm1(rv, rk, cnt, s.ids + ro, s.sc + ro, olen2, hk, hv, mf, 2 * Lp,
                    [&](int32_t id) { return s.key(id); });
   }
@@ -426,12 +435,15 @@ __device__ __forceinline__ void finish_source(int v, int U, KeyAt keyat, ValAt v
     // maxDiff only grows: skip the contended atomic when a larger value is already published
     const unsigned long long b = (unsigned long long)dbits(d1);
     if (b > __hip_atomic_load(maxdiff, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(maxdiff, b);
+    // (rare once the baskets are full: lengths settle within a few updates)
+    if (cnt != oldlen)
+      atomicAdd(&stats[PPR_STAT_LENCHG + (v & (PPR_LENCHG_SHARDS - 1)) * PPR_LENCHG_STRIDE], 1ull);
     if (a.diag) {  // PPR_DIAG: merged rows, and rows left bit-identical (norm1 = 0)
       atomicAdd(&a.diag[150], 1ull);
       if (d1 == 0.0) atomicAdd(&a.diag[151], 1ull);
     }
   }
-  (void)stats;  // written-row bytes are summed by k_stat_written (no per-source atomics)
+  // (written-row bytes are summed by k_stat_written: no per-source atomics)
 }
 
 }  // namespace pprk
