@@ -203,6 +203,10 @@ __host__ __device__ constexpr size_t lds_wave_bytes(int T, int Lp) {
 #define PPR_TW_BATCH 8
 #endif
 constexpr int HUB_TW_BATCH = PPR_TW_BATCH;  // candidate groups a walking wave gathers before using them
+// the walk clears its WAVE * HUB_TW_BATCH flag bytes as HUB_TW_BATCH / 4 words a lane: with any other
+// batch the last groups' flags stay stale, the ballot reads a wrong successor off them and the gather
+// leaves that successor's row
+static_assert(HUB_TW_BATCH > 0 && HUB_TW_BATCH % 4 == 0, "PPR_TW_BATCH must be a positive multiple of 4");
 
 // walk the candidates of successors [i0, e) (at most one per lane) in successor order, 64 per step:
 // f(valid, id, score, one_row) per group: id = the stored id (HOT_TAG-ed for hot keys, DevSlab::key
@@ -294,6 +298,7 @@ __device__ __forceinline__ void hub_window_walk_part(const DevGraph& g, const De
       key[k] = 0;
       sv[k] = 0.0;
       if (valid) {
+        // jj is the successor whose basket holds c (every flag of the batch is fresh): ex <= c < incl[jj]
         const int64_t r = s.row(sj, uj) + (c - ex);
         key[k] = ld_nt(&s.ids[r], a.nt & 1u);
         sv[k] = (a.whatif & WI_SCAT_NOSCORE) ? 0.5 : ld_nt(&s.sc[r], a.nt & 1u);  // (timing only)

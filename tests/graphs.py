@@ -1,0 +1,65 @@
+"""Graph families of the forced-engine matrix that RMAT cannot produce (tests/test_gpu_graph_shapes.py,
+tests/test_graph_shapes_host.py, tools/make_golden.py --g6). Deterministic numpy; every generator
+returns (row_ptr int64 [n + 1], col int32 [m]) with each successor list in the order built here.
+
+  multigraph    repeated successors, unsorted lists, doubled self-loops; node 0 is `hub` copies of one
+                successor (candidates far above distinct keys) and the LAST dense id is a wide source
+  layered       complete layers: every key of a layer carries the same mass, so a cut falls inside a
+                tie of up to G keys
+  rmat_grafted  RMAT plus appended nodes: n is odd, the appended ids close unsorted lists
+"""
+import numpy as np
+
+
+def _csr(lists):
+    rp = np.zeros(len(lists) + 1, dtype=np.int64)
+    rp[1:] = np.cumsum([len(s) for s in lists])
+    col = np.concatenate([np.asarray(s, dtype=np.int32) for s in lists]) if rp[-1] else np.zeros(0, np.int32)
+    return rp, col.astype(np.int32)
+
+
+def multigraph(n, seed, hub=3000, last=None):
+    """node v: d in [1, 24) random successors, the first d // 2 of them repeated 1 to 3 more times,
+    [v, v] appended when v % 7 == 0, the list shuffled; node 0 = [1] * hub + [2, 3, 2]; node n - 1 =
+    `last` (default `hub`) random successors"""
+    rng = np.random.default_rng(seed)
+    lists = []
+    for v in range(n):
+        d = int(rng.integers(1, 24))
+        s = rng.integers(0, n, d).tolist()
+        for u in s[: d // 2]:
+            s.extend([u] * int(rng.integers(1, 4)))
+        if v % 7 == 0:
+            s.extend([v, v])
+        lists.append(rng.permutation(np.asarray(s, dtype=np.int64)).tolist())
+    lists[0] = [1] * hub + [2, 3, 2]
+    lists[n - 1] = rng.integers(0, n, hub if last is None else last).tolist()
+    return _csr(lists)
+
+
+def layered(G, m, half=False):
+    """m layers of G nodes: node v of layer v // G points to all G nodes of the next layer (mod m) and,
+    with `half`, to every second node of the layer after that"""
+    lists = []
+    for v in range(G * m):
+        nxt = ((v // G + 1) % m) * G
+        s = list(range(nxt, nxt + G))
+        if half:
+            nn = ((v // G + 2) % m) * G
+            s.extend(range(nn, nn + G, 2))
+        lists.append(s)
+    return _csr(lists)
+
+
+def rmat_grafted(scale, extra, seed):
+    """ppr.rmat(scale, seed) plus `extra` appended nodes, each with 1 to 40 random successors among the
+    RMAT nodes and appended to the lists of 1 to 40 random RMAT nodes"""
+    import approximated_personalized_pagerank_amd as ppr
+    g = ppr.rmat(scale, seed=seed)
+    rng = np.random.default_rng(seed)
+    lists = [g.col[g.row_ptr[v]:g.row_ptr[v + 1]].tolist() for v in range(g.n)]
+    for x in range(g.n, g.n + extra):
+        lists.append(rng.integers(0, g.n, int(rng.integers(1, 41))).tolist())
+        for v in rng.choice(g.n, int(rng.integers(1, 41)), replace=False):
+            lists[int(v)].append(x)
+    return _csr(lists)

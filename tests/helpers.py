@@ -13,7 +13,7 @@ EXACT = [
     "g1_ring100", "g1_ring100_multi", "g2_rmat8_full", "g5_noedges10", "g5_single", "g5_single_loop",
     "g5_two_linked", "g5_ring6", "g5_ring6_k3l4", "g5_star", "g5_star_loop", "g5_ring100_k10_l10",
     "g5_ring100_k10_l20", "g5_ring100_full", "g5_instar_full", "g5_instar_loop_full",
-    "g5_instar_all_full", "g5_random5000_full", "g5_complete_full",
+    "g5_instar_all_full", "g5_random5000_full", "g5_complete_full", "g6_multigraph_full",
 ]
 # truncating runs: statistical parity (P3/P4, tests/test_parity_p34.py), top-K Jaccard thresholds
 # just under the reference-vs-relabelled-reference agreement (fixture field self_jaccard)

@@ -5,7 +5,7 @@ Runs oracle/_ref/ref_driver (built by `make -C oracle ref` from the unmodified r
 in /root/reference) on graphs produced here, and stores inputs + reference outputs as .npz
 fixtures (data only; no reference source travels). Run from the repo root:
 
-    python tools/make_golden.py
+    python tools/make_golden.py          (--mc, --p34, --g6: only that group of fixtures)
 
 Each fixture holds, in the REFERENCE's graph iteration order (its unordered_map order, which
 defines the dense ids the engine uses): the dense CSR (rp, col), the reference's partition bits
@@ -311,9 +311,22 @@ def main_p34():
     self_ceiling("g3_rmat14_k64_l128", k14, s14)
 
 
+def main_g6():
+    """G6: a multigraph (tests/graphs.py: repeated successors in unsorted lists, doubled self-loops, a
+    node of 700 copies of one successor, a last node of 900 successors), K = L = n so that no basket
+    is cut (a cut at a tie is broken by the reference's hash order: K = 64 differs in one row)"""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import graphs
+    rp, col = graphs.multigraph(256, seed=6, hub=700, last=900)
+    succ = [col[rp[v]:rp[v + 1]].tolist() for v in range(256)]
+    gen_graph("g6_multigraph_full", list(range(256)), succ, 256, 256, 10, 0.85, -1.0)
+
+
 def main():
     if "--mc" in sys.argv:
         return main_mc()
+    if "--g6" in sys.argv:
+        return main_g6()
     if "--p34" in sys.argv:
         return main_p34()
     os.makedirs(GOLDEN, exist_ok=True)
