@@ -21,7 +21,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libppr_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 # every file the library is compiled from (csrc/ plus the public header), in digest order
-CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
+CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
 # every header of csrc/ (a new one can not be left out of the provenance digest) and the C ABI
 CSRC_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "ppr_hip.h")]
 
@@ -57,6 +57,9 @@ PPR_FLAG_STATS = 1
 PPR_FLAG_CHAIN_SUM = 2  # the reference's in-order fma sums instead of the default exact sum
 PPR_QUERY_EXCLUDE_SEEDS = 1  # ppr_grank_plan_query: drop a query's own seeds from its result
 PPR_RQUERY_EXCLUDE_TARGETS = 1  # ppr_grank_plan_rquery: drop the sources that are targets of the query
+PPR_PROP_F32, PPR_PROP_BF16 = 0, 1  # ppr_grank_plan_propagate(_t): feature dtype
+PPR_PROP_ROW_NORMALIZE = 1  # ... weights s_j / W, W the row's scores summed in stored order
+PPR_PROP_CHUNK = 512  # postings per chunk of the transposed sum (part of the contract)
 
 ERRORS = {
     0: "ok",
@@ -146,6 +149,17 @@ class PprRQueryStats(ctypes.Structure):
     ]
 
 
+class PprPropStats(ctypes.Structure):
+    _fields_ = [
+        ("device_ms", ctypes.c_double),
+        ("postings", ctypes.c_int64),
+        ("algo_bytes", ctypes.c_int64),
+        ("passes", ctypes.c_int64),
+        ("chunks", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -188,6 +202,9 @@ def lib() -> ctypes.CDLL:
         "ppr_grank_plan_fetch_rows": (ctypes.c_int, [vp, i64, i64, vp, vp, vp]),
         "ppr_grank_plan_query": (ctypes.c_int, [vp, i32, i64, vp, vp, vp, u32, u32, vp, vp, vp, vp]),
         "ppr_grank_plan_rquery": (ctypes.c_int, [vp, i32, i64, vp, vp, vp, u32, u32, vp, vp, vp, vp]),
+        "ppr_grank_plan_propagate": (ctypes.c_int, [vp, i32, i64, vp, i32, i32, u32, vp, i64, vp, i64, vp]),
+        "ppr_grank_plan_propagate_t": (ctypes.c_int, [vp, i32, i64, vp, i32, i32, u32, vp, i64, vp, i64, vp]),
+        "ppr_grank_plan_device": (ctypes.c_int, [vp, ctypes.POINTER(i32)]),
         "ppr_host_alloc": (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
         "ppr_host_free": (None, [vp]),
         "ppr_grank_plan_stream": (vp, [vp]),

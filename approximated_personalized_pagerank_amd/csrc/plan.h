@@ -359,6 +359,12 @@ struct ppr_plan {
   unsigned char* d_rl = nullptr;      // hit lists and the levels of their reduction
   unsigned char* d_rt = nullptr;      // reduction tasks
   size_t r_bytes = 0, rl_bytes = 0, rt_bytes = 0;
+  // feature propagation (propagate.hip): grow-only and kept across calls as well
+  unsigned char* d_p = nullptr;       // a call's sources, per-position counts, offsets and row sums
+  unsigned char* d_pk = nullptr;      // per-key posting counts and their shards (calls of more than one pass)
+  unsigned char* d_ps = nullptr;      // a pass's postings, both sort buffers, digit counts, run starts
+  unsigned char* d_pt = nullptr;      // a pass's chunk and fold tasks, partial rows
+  size_t p_bytes = 0, pk_bytes = 0, ps_bytes = 0, pt_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -423,6 +429,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_wl);
   hipFree(p->d_q); hipFree(p->d_ql);
   hipFree(p->d_r); hipFree(p->d_rl); hipFree(p->d_rt);
+  hipFree(p->d_p); hipFree(p->d_pk); hipFree(p->d_ps); hipFree(p->d_pt);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (p->ev_rp) hipEventDestroy(p->ev_rp);

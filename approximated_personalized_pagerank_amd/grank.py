@@ -339,3 +339,121 @@ class GrankPlan:
                                                     ctypes.byref(st)), "plan_rquery")
         return RQueryResult(ids, sc, lens, float(st.device_ms), int(st.hits), int(st.algo_bytes),
                             int(st.probe_queries), int(st.scan_queries), int(st.scans), int(st.chunks))
+
+    # ---- feature propagation (include/ppr_hip.h ppr_grank_plan_propagate / _propagate_t) ----
+    @property
+    def device(self) -> int:
+        """HIP device ordinal the plan lives on"""
+        d = ctypes.c_int32()
+        _lib.check(_lib.lib().ppr_grank_plan_device(self._p, ctypes.byref(d)), "plan_device")
+        return int(d.value)
+
+    def _prop_sources(self, sources):
+        """(S, int32 array or None) of a propagate call"""
+        if sources is None:
+            return self.csr.n, None
+        try:
+            import torch
+            if isinstance(sources, torch.Tensor):
+                sources = sources.detach().cpu().numpy()
+        except ImportError:  # (a caller without torch passes arrays or lists)
+            pass
+        flat = np.asarray(sources, dtype=np.int64).reshape(-1)
+        if len(flat) and (flat.min() < -2**31 or flat.max() >= 2**31):
+            raise ValueError("source ids must fit in int32")
+        return len(flat), np.ascontiguousarray(flat, dtype=np.int32)
+
+    def _prop_tensor(self, t, rows: int, what: str, dtype=None, cols=None):
+        """every refusal of a feature tensor, before any C call: a wrong shape would be an
+        out-of-bounds access on the device"""
+        import torch
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{what} must be a torch.Tensor on the plan's device")
+        if not t.is_cuda or t.device.index != self.device:
+            raise ValueError(f"{what} is on {t.device}, the plan on device {self.device}")
+        if t.dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"{what} must be float32 or bfloat16, not {t.dtype}")
+        if dtype is not None and t.dtype != dtype:
+            raise TypeError(f"{what} is {t.dtype}, the input {dtype}")
+        if t.dim() != 2:
+            raise ValueError(f"{what} must be 2-D, not {t.dim()}-D")
+        if t.shape[0] != rows:
+            raise ValueError(f"{what} has {t.shape[0]} rows, expected {rows}")
+        if cols is not None and t.shape[1] != cols:
+            raise ValueError(f"{what} has {t.shape[1]} columns, expected {cols}")
+        if t.shape[1] > 1 and t.stride(1) != 1:
+            raise ValueError(f"{what}: rows must be contiguous (stride {t.stride(1)})")
+        if t.shape[0] > 1 and t.stride(0) < t.shape[1]:
+            raise ValueError(f"{what}: row stride {t.stride(0)} below its {t.shape[1]} columns")
+        return t
+
+    def _propagate(self, fn_name, X, in_rows, out_rows, S, src, normalize, iterations_run, out, stats):
+        import torch
+        X = self._prop_tensor(X, in_rows, "the input")
+        F = int(X.shape[1])
+        if out is None:
+            out = torch.empty((out_rows, F), dtype=X.dtype, device=X.device)
+        else:
+            self._prop_tensor(out, out_rows, "out", X.dtype, F)
+        X, out_raw = X.detach(), out.detach()  # (views of the same memory: nothing here is recorded)
+        it = self.iterations_run if iterations_run is None else iterations_run
+        dt = _lib.PPR_PROP_BF16 if X.dtype == torch.bfloat16 else _lib.PPR_PROP_F32
+        st = _lib.PprPropStats()
+        ldx = int(X.stride(0)) if X.shape[0] > 1 else max(F, 1)
+        ldo = int(out_raw.stride(0)) if out_raw.shape[0] > 1 else max(F, 1)
+        # a pointer for an empty tensor too: the C call refuses null pointers, and reads nothing through it
+        xp = X.data_ptr() or out_raw.data_ptr() or 1
+        op = out_raw.data_ptr() or xp
+        torch.cuda.current_stream(X.device).synchronize()  # H / G are complete before the plan's stream reads them
+        fn = getattr(_lib.lib(), fn_name)
+        _lib.check(fn(self._p, it, S, _lib.ptr(src), F, dt, _lib.PPR_PROP_ROW_NORMALIZE if normalize else 0,
+                      xp, ldx, op, ldo, ctypes.byref(st)), fn_name)
+        if stats is not None:
+            stats.update(device_ms=float(st.device_ms), postings=int(st.postings), algo_bytes=int(st.algo_bytes),
+                         passes=int(st.passes), chunks=int(st.chunks))
+        return out
+
+    def propagate(self, H, sources=None, normalize: bool = False, iterations_run: Optional[int] = None, out=None,
+                  stats: Optional[dict] = None):
+        """Z = B[sources] H on the device: row i of the result aggregates the feature rows of the
+        keys of source i's basket, weighted by their scores (`normalize`: by score / row sum), in
+        fp64, rounded once to H's dtype (float32 or bfloat16). H: torch tensor [n, F] on the plan's
+        device; sources: dense ids (None: every node, in order); out: optional [S, F] tensor of the
+        same dtype (a row stride above F is fine); stats: a dict that receives the call's
+        ppr_prop_stats. Returns the [S, F] tensor. The C call runs on the plan's stream and returns
+        when it is done."""
+        S, src = self._prop_sources(sources)
+        return self._propagate("ppr_grank_plan_propagate", H, self.csr.n, S, S, src, normalize, iterations_run, out,
+                               stats)
+
+    def propagate_t(self, G, sources=None, normalize: bool = False, iterations_run: Optional[int] = None, out=None,
+                    stats: Optional[dict] = None):
+        """Y = B[sources]^T G, the adjoint of propagate(): G is [S, F], the result [n, F] (every row
+        written; keys no source of the batch holds get zeros). Bitwise reproducible: per key the
+        postings are summed in ascending position, in chunks of 512, without float atomics."""
+        S, src = self._prop_sources(sources)
+        return self._propagate("ppr_grank_plan_propagate_t", G, S, self.csr.n, S, src, normalize, iterations_run, out,
+                               stats)
+
+
+def propagate(plan: GrankPlan, H, sources=None, normalize: bool = False):
+    """Differentiable plan.propagate(H, sources, normalize): a torch.autograd.Function whose
+    backward is plan.propagate_t(grad, sources, normalize) with the iteration count captured at the
+    forward. No gradient flows into the table."""
+    import torch
+
+    it = plan.iterations_run
+    S, src = plan._prop_sources(sources)
+
+    class _Propagate(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, h):
+            return plan.propagate(h, src, normalize, it)
+
+        @staticmethod
+        def backward(ctx, grad):
+            if not grad.is_contiguous():
+                grad = grad.contiguous()  # (an expanded cotangent, as .sum() produces)
+            return plan.propagate_t(grad, src, normalize, it)
+
+    return _Propagate.apply(H)

@@ -317,6 +317,64 @@ int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_t Q, const 
                           const int32_t* targets, const double* weights, uint32_t Kq, uint32_t flags,
                           int32_t* out_sources, double* out_scores, int32_t* out_len, ppr_rquery_stats* st);
 
+/* ---- feature propagation through the resident table, both ways ----
+ * The dense products of the same table (no reference counterpart): Z = B[S] H, the PPRGo / APPNP
+ * style aggregation of node features H [n, F] over the top-L PPR rows of a batch of S sources
+ * (Bojchevski et al., "Scaling Graph Neural Networks with Approximate PageRank"), and its adjoint
+ * Y = B[S]^T G for training through it. H / Z / G / Y are DEVICE pointers (everything else is host
+ * memory): the table is not downloaded and the features are not staged through the host.
+ * Common to both directions. GRank plans only. B[u] is the current row of u after `iterations_run`
+ * iterations (the slot rule of ppr_grank_plan_fetch_slab; stored ids decoded to keys; the row
+ * length clamped to [0, L]). Its entries (k_j, s_j), j = 0 .. len - 1, are taken in STORED ORDER,
+ * ascending hash_b(k) (csrc/ppr_device.h): a function of the row's key set alone, not of the engine
+ * that wrote the row. dt is PPR_PROP_F32 or PPR_PROP_BF16, shared by the input and the output of a
+ * call; every sum is carried in fp64 and rounded to dt ONCE, to nearest even (bf16 straight from
+ * the fp64 value, not through fp32). Weights w_j = s_j; with PPR_PROP_ROW_NORMALIZE
+ * W = ((0.0 + s_0) + s_1) + ... in stored order with plain fp64 adds and w_j = s_j / W (one fp64
+ * divide per entry), w_j = 0 when W == 0. sources: S dense ids (host), repeats allowed; NULL: S must
+ * equal n and position i is source i.
+ * Forward, ppr_grank_plan_propagate: H has n rows of F values with row stride ldh elements, Z has S
+ * rows with stride ldz. For position i with u = sources[i] and every column c: acc = +0.0; for j in
+ * stored order acc = fma(w_j, (double)H[k_j][c], acc) (an explicit fma); Z[i][c] = round_dt(acc).
+ * A row of length 0 gives zeros.
+ * Transposed, ppr_grank_plan_propagate_t: G has S rows with stride ldg, Y has n rows with stride
+ * ldy; EVERY row of Y is written (a key no row of the batch holds gets zeros). The postings of key
+ * k are all (i, w) such that k is a key of B[sources[i]], in ascending position i (keys are distinct
+ * within a row: at most one posting per position). A key's list is cut into chunks of
+ * PPR_PROP_CHUNK = 512 postings -- a constant of the contract; chunk m computes p_m = the fma chain
+ * from +0.0 over its postings in order, acc = fma(w, (double)G[i][c], acc); the total is
+ * ((p_0 + p_1) + p_2) ... with plain fp64 adds in chunk order; Y[k][c] = round_dt(total). No float
+ * atomics are used: the result is bitwise reproducible.
+ * Either result depends only on the slab and the arguments -- not on tiling, batching, knobs or the
+ * order of anything -- and the calls write nothing into the slabs or the plan's top-K output.
+ * Synchronous on the plan's stream (the caller synchronises the stream that produced H / G first).
+ * Errors, all decided on the host before any kernel starts: PPR_ERR_ARG (null plan or pointers,
+ * S < 0, NULL sources with S != n, a stride below F, F < 0, unknown dtype or flag bits, an MC plan),
+ * PPR_ERR_RANGE (F == 0, F > 8192, or S > 2^30: positions are 32-bit), PPR_ERR_SOURCE (a source
+ * outside [0, n)).
+ * Stats: postings = sum of len over the positions (forward) / postings sorted (transposed);
+ * algo_bytes = the bytes the algorithm has to move: per posting 12 (id and score) +
+ * F * sizeof(dt) (the gathered feature row); per output row (S forward, n transposed)
+ * F * sizeof(dt); per position 8. passes = key-range passes (1 forward), chunks = chunk tasks
+ * (0 forward). ppr_grank_plan_device: the HIP device ordinal the plan lives on. */
+enum { PPR_PROP_F32 = 0, PPR_PROP_BF16 = 1 };
+enum { PPR_PROP_ROW_NORMALIZE = 1 };
+#define PPR_PROP_CHUNK 512
+typedef struct ppr_prop_stats {
+  double device_ms;          /* HIP events around the kernels; uploads and downloads excluded */
+  int64_t postings;
+  int64_t algo_bytes;        /* see above */
+  int64_t passes;
+  int32_t chunks; int32_t reserved;
+} ppr_prop_stats;
+int ppr_grank_plan_propagate(ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources,
+                             int32_t F, int32_t dt, uint32_t flags, const void* H, int64_t ldh, void* Z,
+                             int64_t ldz, ppr_prop_stats* st);
+int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources,
+                               int32_t F, int32_t dt, uint32_t flags, const void* G, int64_t ldg, void* Y,
+                               int64_t ldy, ppr_prop_stats* st);
+int ppr_grank_plan_device(ppr_plan* p, int32_t* device);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
