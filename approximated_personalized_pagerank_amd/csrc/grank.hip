@@ -54,6 +54,7 @@
 using namespace pprk;
 
 #include "plan.h"
+#include "resident_call.h"
 #include "host_par.h"
 
 namespace pprk {
@@ -801,8 +802,9 @@ static IterArgs iter_args(const ppr_plan* p, int it, bool unit) {
   a.xs = p->xsum ? 1u : 0u;
   a.xsf = XS_F;
   if (unit) { a.sA = 0; a.sB = 0; a.active = -1; return a; }
-  a.sA = ((it + 1) / 2) & 1;
-  a.sB = (it / 2) & 1;
+  const pprres::SlotPair sp = pprres::slot_pair(it);
+  a.sA = sp.sA;
+  a.sB = sp.sB;
   a.active = it & 1;
   return a;
 }
@@ -2893,22 +2895,16 @@ extern "C" int ppr_grank_plan_read_maxdiff(ppr_plan* p, int32_t it, double* maxd
   return PPR_OK;
 }
 
-// this module's bounded-probe error word (ppr_device.h probe_fail): PPR_ERR_PROBE once set (and
-// cleared), read once per run (a device-wide sync)
-int probe_take() {
-  unsigned int v = 0u;
-  HIP_OK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_probe_err), sizeof(v), 0, hipMemcpyDeviceToHost));
-  if (!v) return PPR_OK;
-  const unsigned int z = 0u;
-  HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_err), &z, sizeof(z), 0, hipMemcpyHostToDevice));
-  return PPR_ERR_PROBE;
-}
+// this module's bounded-probe error word, for mccp2.hip too (its combine runs this module's merge
+// kernels); read once per run
+int probe_take() { return take_probe_err(); }
 
 extern "C" int ppr_grank_plan_finish(ppr_plan* p, int32_t iterations_run) {
   if (!p || iterations_run < 0) return PPR_ERR_ARG;
   if (p->n == 0) return PPR_OK;
   HIP_OK(hipSetDevice(p->device));
-  const int rc = launch_topk(p, ((iterations_run + 1) / 2) & 1, (iterations_run / 2) & 1, nullptr, 0);
+  const pprres::SlotPair sp = pprres::slot_pair(iterations_run);
+  const int rc = launch_topk(p, sp.sA, sp.sB, nullptr, 0);
   if (rc) return rc;
   return probe_take();
 }
@@ -3040,7 +3036,8 @@ extern "C" int ppr_grank_plan_fetch_slab(ppr_plan* p, int32_t iterations_run, in
                                          double* scores, int32_t* len) {
   if (!p || iterations_run < 0) return PPR_ERR_ARG;
   HIP_OK(hipSetDevice(p->device));
-  const int sA = ((iterations_run + 1) / 2) & 1, sB = (iterations_run / 2) & 1;
+  const pprres::SlotPair sp = pprres::slot_pair(iterations_run);
+  const int sA = sp.sA, sB = sp.sB;
   hipStream_t st = p->stream;
   HIP_OK(hipStreamSynchronize(st));  // the plan's stream is non-blocking: drain it first
   std::vector<uint8_t> part(p->n);
@@ -3711,7 +3708,8 @@ extern "C" int ppr_grank_plan_ends_time(ppr_plan* p, int32_t world, int32_t rank
     }
     HIP_OK(hipGetLastError());
     HIP_OK(hipEventRecord(p->ev_a, s));
-    int rc = launch_topk(p, ((iterations_run + 1) / 2) & 1, (iterations_run / 2) & 1, p->d_xowner, rank);
+    const pprres::SlotPair sp = pprres::slot_pair(iterations_run);
+    int rc = launch_topk(p, sp.sA, sp.sB, p->d_xowner, rank);
     if (rc) return rc;
   } else {
     const int64_t m0 = bd[0][rank + 1] - bd[0][rank], m1 = bd[1][rank + 1] - bd[1][rank];
@@ -3789,7 +3787,8 @@ static int run_sharded_impl(ppr_plan* p, uint32_t iterations, double tolerance, 
   if (shard_ends) {
     rc = x_sync(p, s);  // (init / last exchange)
     if (rc) return rc;
-    rc = launch_topk(p, ((it + 1) / 2) & 1, (it / 2) & 1, p->d_xowner, p->rank);
+    const pprres::SlotPair sp = pprres::slot_pair(it);
+    rc = launch_topk(p, sp.sA, sp.sB, p->d_xowner, p->rank);
     if (rc) return rc;
     for (int q = 0; q < 2; q++) {
       rc = x_gather_topk(p, q, bd[q]);

@@ -24,7 +24,7 @@
 #include <new>
 #include <vector>
 
-#include "plan.h"
+#include "resident_call.h"
 #include "merge_mc.h"
 
 namespace {
@@ -223,14 +223,7 @@ extern "C" int ppr_mccp2_plan_combine(ppr_plan* p) {
     const int rc = probe_take();
     if (rc) return rc;
   }
-  unsigned int v = 0u;
-  HIP_OK(hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_probe_err), sizeof(v), 0, hipMemcpyDeviceToHost));
-  if (v) {
-    const unsigned int z = 0u;
-    HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_err), &z, sizeof(z), 0, hipMemcpyHostToDevice));
-    return PPR_ERR_PROBE;
-  }
-  return PPR_OK;
+  return take_probe_err();
 }
 
 extern "C" int ppr_mccp2_plan_run(ppr_plan* p, uint32_t walks, uint64_t seed, ppr_mc_stats* st) {

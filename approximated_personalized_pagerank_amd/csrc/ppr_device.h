@@ -19,6 +19,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "hash32.h"
+
 namespace pprd {
 
 constexpr int WAVE = 64;
@@ -40,10 +42,7 @@ __device__ __forceinline__ double bitsd(uint64_t x) { return __longlong_as_doubl
 static __device__ unsigned int g_probe_err = 0u;
 __device__ __forceinline__ void probe_fail() { atomicOr(&g_probe_err, 1u); }
 
-__device__ __forceinline__ uint32_t hash32(uint32_t x) {
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
+// hash32: hash32.h (host and device, one definition)
 
 // the basket-row order and the hub key-bucket digit: rows are stored by ascending hash_b(key)
 // (a bijection of the 32-bit id space, so distinct keys never tie)

@@ -29,8 +29,8 @@
 //   k_p_zero<DT>    the range's keys without postings: zero rows
 // No float atomics anywhere; every index is bounded (positions and keys clamped or skipped).
 #pragma once
-#include "ppr_common.h"
 #include "prop_plan.h"
+#include "resident.h"
 
 namespace pprk {
 
@@ -52,20 +52,7 @@ __device__ __forceinline__ int p_src(const DevSlab& s, const PArgs& a, int64_t i
   int64_t u = a.src ? (int64_t)a.src[i] : i;  // (checked on the host; clamped all the same)
   return (int)(u < 0 ? 0 : u >= s.n ? s.n - 1 : u);
 }
-__device__ __forceinline__ int p_len(const DevSlab& s, int slot, int64_t u) {  // (q_len's clamp)
-  const int len = s.len[s.lrow(slot, u)];
-  return len < 0 ? 0 : len > s.L ? s.L : len;
-}
-// stored id -> key, -1 for an id no key stands behind (skipped by every kernel alike)
-template <bool HK>
-__device__ __forceinline__ int p_key(const DevSlab& s, int32_t id) {
-  if (id >= 0) return (int64_t)id < s.n ? id : -1;
-  if (!HK) return -1;
-  const uint32_t h = (uint32_t)id & 0x7fffffffu;
-  if ((int)h >= s.hn) return -1;
-  const int k = s.hkeys[h];
-  return k >= 0 && (int64_t)k < s.n ? k : -1;
-}
+// (slot, length and stored id -> key: resident.h; an id no key stands behind is skipped by every kernel alike)
 
 // ---- feature elements: DT 0 = fp32, 1 = bf16 ---------------------------------------------------
 // V elements of one lane, as loaded
@@ -203,8 +190,8 @@ __global__ void __launch_bounds__(P_THREADS) k_p_fwd(DevSlab s, PArgs a, const v
   int64_t row = 0;
   if (i < a.S) {
     const int u = p_src(s, a, i);
-    const int slot = a.part[u] ? a.sB : a.sA;
-    len = p_len(s, slot, u);
+    const int slot = res_slot(a.part, a.sA, a.sB, u);
+    len = res_len(s, slot, u);
     row = s.row(slot, u);
   }
   double W = 0.0;
@@ -220,7 +207,7 @@ __global__ void __launch_bounds__(P_THREADS) k_p_fwd(DevSlab s, PArgs a, const v
     int key = -1;
     double wt = 0.0;
     if (b + j < len) {
-      key = p_key<HK>(s, s.ids[row + b + j]);
+      key = res_key<HK>(s, s.ids[row + b + j]);
       const double sc = s.sc[row + b + j];
       wt = a.norm ? pprprop::prop_weight(sc, W) : sc;
     }
@@ -235,8 +222,8 @@ __global__ void __launch_bounds__(P_THREADS) k_p_len(DevSlab s, PArgs a, double*
   unsigned long long len = 0ull;
   if (i < a.S) {
     const int u = p_src(s, a, i);
-    const int slot = a.part[u] ? a.sB : a.sA;
-    const int n = p_len(s, slot, u);
+    const int slot = res_slot(a.part, a.sA, a.sB, u);
+    const int n = res_len(s, slot, u);
     len = (unsigned long long)n;
     if (wpos) {
       const int64_t row = s.row(slot, u);
@@ -264,8 +251,8 @@ __global__ void __launch_bounds__(P_THREADS) k_p_walk(DevSlab s, PArgs a, int lg
   int64_t row = 0;
   if (i < a.S) {
     const int u = p_src(s, a, i);
-    const int slot = a.part[u] ? a.sB : a.sA;
-    len = p_len(s, slot, u);
+    const int slot = res_slot(a.part, a.sA, a.sB, u);
+    len = res_len(s, slot, u);
     row = s.row(slot, u);
   }
   int maxlen = len;
@@ -277,7 +264,7 @@ __global__ void __launch_bounds__(P_THREADS) k_p_walk(DevSlab s, PArgs a, int lg
   for (int b = 0; b < maxlen; b += G) {
     const int e = b + j;
     int key = -1;
-    if (e < len) key = p_key<HK>(s, s.ids[row + e]);
+    if (e < len) key = res_key<HK>(s, s.ids[row + e]);
     const bool hit = key >= k0 && key < k1;
     const uint64_t gm = (__ballot(hit) >> g0) & gmask;
     if (hit) {
@@ -430,8 +417,8 @@ __global__ void __launch_bounds__(P_THREADS) k_p_tsum(DevSlab s, PArgs a, const 
       const int jj = (int)(v & ((1 << P_JBITS) - 1));
       if (i >= 0 && i < a.S) {
         const int u = p_src(s, a, i);
-        const int slot = a.part[u] ? a.sB : a.sA;
-        if (jj < p_len(s, slot, u)) {
+        const int slot = res_slot(a.part, a.sA, a.sB, u);
+        if (jj < res_len(s, slot, u)) {
           const double sc = s.sc[s.row(slot, u) + jj];
           wt = a.norm ? pprprop::prop_weight(sc, wpos[i]) : sc;
           pos = (int)i;

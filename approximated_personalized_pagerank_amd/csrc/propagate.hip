@@ -18,6 +18,8 @@
 // postings and cut_key_ranges the passes. Per pass: count per position, scan, emit in position-major
 // order, stable sort by key, run starts, the lists cut into chunk tasks (k_p_tcount, three scans,
 // k_p_tplan), k_p_tsum / k_p_tfold / k_p_zero write the range's rows of Y.
+// The id-range check and the slot rule are resident_args.h's, the scratch and timing plumbing
+// resident_call.h's; both are shared with query.hip and rquery.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -26,7 +28,7 @@
 
 #include <hipcub/hipcub.hpp>
 
-#include "plan.h"
+#include "resident_call.h"
 #include "propagate.h"
 
 namespace {
@@ -38,36 +40,6 @@ using pprprop::PTask;
 
 constexpr int64_t P_ENTRIES_DEFAULT = 1 << 24, P_ENTRIES_MAX = 1 << 30;
 constexpr int P_MAX_F = 8192;
-
-size_t rnd256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(base + off);
-    off += rnd256(n * sizeof(T));
-    return r;
-  }
-};
-
-// grow-only device buffer
-int ensure_p(unsigned char** ptr, size_t* cap, size_t need) {
-  if (need <= *cap) return PPR_OK;
-  if (*ptr) hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  need += need / 4 + 4096;
-  if (hipMalloc((void**)ptr, need) != hipSuccess) return PPR_ERR_OOM;
-  *cap = need;
-  return PPR_OK;
-}
-
-int64_t env_i64(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
 
 // what both directions refuse; sz = bytes of an element
 int check_common(const ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources, int32_t F, int32_t dt,
@@ -81,10 +53,7 @@ int check_common(const ppr_plan* p, int32_t iterations_run, int64_t S, const int
   if (F > P_MAX_F) return PPR_ERR_RANGE;
   if (ldin < F || ldout < F) return PPR_ERR_ARG;
   if (S > P_ENTRIES_MAX) return PPR_ERR_RANGE;  // positions and per-pass offsets are 32-bit
-  if (sources)
-    for (int64_t i = 0; i < S; i++)
-      if (sources[i] < 0 || (int64_t)sources[i] >= p->n) return PPR_ERR_SOURCE;
-  return PPR_OK;
+  return sources ? pprres::check_ids(sources, S, p->n) : PPR_OK;
 }
 
 // columns per lane: the widest of 16 / 8 bytes that F, both strides and both pointers allow
@@ -105,59 +74,43 @@ int pick_lgG(int64_t need) {
   return lgG;
 }
 
-struct PCall {
-  ppr_plan* p;
-  hipStream_t s;
-  DevSlab slab;
-  PArgs a;
-  double dev_ms = 0.0;
-  int lap() {  // kernels between ev_m0 and ev_m1 (waits for them)
-    HIP_OK(hipEventRecord(p->ev_m1, s));
-    HIP_OK(hipEventSynchronize(p->ev_m1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, p->ev_m0, p->ev_m1));
-    dev_ms += ms;
-    return PPR_OK;
-  }
-};
-
 // the call's sources on the device and the slot rule
-int begin_call(PCall& c, ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources, uint32_t flags,
-               size_t extra_bytes) {
-  HIP_OK(hipSetDevice(p->device));
-  c.p = p;
-  c.s = p->stream;
-  c.slab = dev_slab(p);
+int begin_call(ResidentCall& c, PArgs& a, ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources,
+               uint32_t flags, size_t extra_bytes) {
   {
-    const int rc = ensure_p(&p->d_p, &p->p_bytes, rnd256(4 * (size_t)std::max<int64_t>(S, 1)) + extra_bytes);
+    const int rc = c.begin(p, iterations_run);
     if (rc) return rc;
   }
-  std::memset(&c.a, 0, sizeof(c.a));
-  c.a.part = p->d_part;
-  c.a.sA = ((iterations_run + 1) / 2) & 1;
-  c.a.sB = (iterations_run / 2) & 1;
-  c.a.S = S;
-  c.a.norm = (flags & PPR_PROP_ROW_NORMALIZE) ? 1 : 0;
-  c.a.src = nullptr;
+  {
+    const int rc = ensure_scratch(&p->d_p, &p->p_bytes, rnd256(4 * (size_t)std::max<int64_t>(S, 1)) + extra_bytes);
+    if (rc) return rc;
+  }
+  std::memset(&a, 0, sizeof(a));
+  a.part = p->d_part;
+  a.sA = c.sA;
+  a.sB = c.sB;
+  a.S = S;
+  a.norm = (flags & PPR_PROP_ROW_NORMALIZE) ? 1 : 0;
+  a.src = nullptr;
   if (sources && S > 0) {
     HIP_OK(hipMemcpyAsync(p->d_p, sources, 4 * (size_t)S, hipMemcpyHostToDevice, c.s));
-    c.a.src = reinterpret_cast<const int32_t*>(p->d_p);
+    a.src = reinterpret_cast<const int32_t*>(p->d_p);
   }
   return PPR_OK;
 }
 
 template <int DT, int V>
-void launch_fwd(const PCall& c, bool hk, dim3 grid, const void* H, int64_t ldh, void* Z, int64_t ldz, int F, int lgG,
-                int64_t ngrp) {
-  if (hk) hipLaunchKernelGGL((k_p_fwd<DT, V, true>), grid, dim3(P_THREADS), 0, c.s, c.slab, c.a, H, ldh, Z, ldz, F, lgG, ngrp);
-  else hipLaunchKernelGGL((k_p_fwd<DT, V, false>), grid, dim3(P_THREADS), 0, c.s, c.slab, c.a, H, ldh, Z, ldz, F, lgG, ngrp);
+void launch_fwd(const ResidentCall& c, const PArgs& a, bool hk, dim3 grid, const void* H, int64_t ldh, void* Z,
+                int64_t ldz, int F, int lgG, int64_t ngrp) {
+  if (hk) hipLaunchKernelGGL((k_p_fwd<DT, V, true>), grid, dim3(P_THREADS), 0, c.s, c.slab, a, H, ldh, Z, ldz, F, lgG, ngrp);
+  else hipLaunchKernelGGL((k_p_fwd<DT, V, false>), grid, dim3(P_THREADS), 0, c.s, c.slab, a, H, ldh, Z, ldz, F, lgG, ngrp);
 }
 
 template <int DT, int V>
-void launch_tsum(const PCall& c, dim3 grid, const double* wpos, const PTask* tasks, int64_t nt, const int64_t* vals, int M,
-                 const void* G, int64_t ldg, void* Y, int64_t ldy, double* parts, int64_t nparts, int64_t ldp, int c0,
-                 int c1) {
-  hipLaunchKernelGGL((k_p_tsum<DT, V>), grid, dim3(P_THREADS), 0, c.s, c.slab, c.a, wpos, tasks, nt, vals, M, G, ldg, Y, ldy,
+void launch_tsum(const ResidentCall& c, const PArgs& a, dim3 grid, const double* wpos, const PTask* tasks, int64_t nt,
+                 const int64_t* vals, int M, const void* G, int64_t ldg, void* Y, int64_t ldy, double* parts,
+                 int64_t nparts, int64_t ldp, int c0, int c1) {
+  hipLaunchKernelGGL((k_p_tsum<DT, V>), grid, dim3(P_THREADS), 0, c.s, c.slab, a, wpos, tasks, nt, vals, M, G, ldg, Y, ldy,
                      parts, nparts, ldp, c0, c1);
 }
 
@@ -179,9 +132,10 @@ extern "C" int ppr_grank_plan_propagate(ppr_plan* p, int32_t iterations_run, int
     if (rc) return rc;
   }
   if (S == 0 || p->n == 0) return PPR_OK;
-  PCall c;
+  ResidentCall c;
+  PArgs a;
   {
-    const int rc = begin_call(c, p, iterations_run, S, sources, flags, rnd256(8));
+    const int rc = begin_call(c, a, p, iterations_run, S, sources, flags, rnd256(8));
     if (rc) return rc;
   }
   const int esz = dt == PPR_PROP_BF16 ? 2 : 4;
@@ -194,18 +148,18 @@ extern "C" int ppr_grank_plan_propagate(ppr_plan* p, int32_t iterations_run, int
   unsigned long long* d_tot = reinterpret_cast<unsigned long long*>(p->d_p + rnd256(4 * (size_t)S));
   if (st) {  // the postings of the batch (outside the timed span)
     HIP_OK(hipMemsetAsync(d_tot, 0, 8, c.s));
-    hipLaunchKernelGGL(k_p_len, dim3((unsigned)((S + P_THREADS - 1) / P_THREADS)), dim3(P_THREADS), 0, c.s, c.slab, c.a,
+    hipLaunchKernelGGL(k_p_len, dim3((unsigned)((S + P_THREADS - 1) / P_THREADS)), dim3(P_THREADS), 0, c.s, c.slab, a,
                        (double*)nullptr, d_tot);
     HIP_OK(hipGetLastError());
   }
   HIP_OK(hipEventRecord(p->ev_m0, c.s));
   if (dt == PPR_PROP_F32) {
-    if (V == 4) launch_fwd<0, 4>(c, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
-    else launch_fwd<0, 1>(c, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
+    if (V == 4) launch_fwd<0, 4>(c, a, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
+    else launch_fwd<0, 1>(c, a, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
   } else {
-    if (V == 8) launch_fwd<1, 8>(c, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
-    else if (V == 4) launch_fwd<1, 4>(c, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
-    else launch_fwd<1, 1>(c, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
+    if (V == 8) launch_fwd<1, 8>(c, a, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
+    else if (V == 4) launch_fwd<1, 4>(c, a, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
+    else launch_fwd<1, 1>(c, a, hk, grid, H, ldh, Z, ldz, F, lgG, ngrp);
   }
   HIP_OK(hipGetLastError());
   {
@@ -251,10 +205,11 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
   const unsigned wgrid = (unsigned)((ngrp + P_WPB - 1) / P_WPB);
   const size_t Sx = (size_t)std::max<int64_t>(S, 1);
 
-  PCall c;
+  ResidentCall c;
+  PArgs a;
   {
     const size_t extra = rnd256(4 * (Sx + 1)) * 2 + rnd256(8 * Sx) + rnd256(8);
-    const int rc = begin_call(c, p, iterations_run, S, sources, flags, extra);
+    const int rc = begin_call(c, a, p, iterations_run, S, sources, flags, extra);
     if (rc) return rc;
   }
   hipStream_t s = c.s;
@@ -270,7 +225,7 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
   if (S > 0) {
     HIP_OK(hipMemsetAsync(d_tot, 0, 8, s));
     HIP_OK(hipEventRecord(p->ev_m0, s));
-    hipLaunchKernelGGL(k_p_len, dim3((unsigned)((S + P_THREADS - 1) / P_THREADS)), dim3(P_THREADS), 0, s, c.slab, c.a,
+    hipLaunchKernelGGL(k_p_len, dim3((unsigned)((S + P_THREADS - 1) / P_THREADS)), dim3(P_THREADS), 0, s, c.slab, a,
                        norm ? wpos : (double*)nullptr, d_tot);
     HIP_OK(hipGetLastError());
     const int rc = c.lap();
@@ -284,16 +239,16 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
   if ((int64_t)tot <= E) {
     ranges.push_back(KeyRange{0, n, (int64_t)tot});
   } else {
-    const int rc = ensure_p(&p->d_pk, &p->pk_bytes, rnd256(4 * (size_t)n) * (PS_SHARDS + 1));
+    const int rc = ensure_scratch(&p->d_pk, &p->pk_bytes, rnd256(4 * (size_t)n) * (PS_SHARDS + 1));
     if (rc) return rc;
     Carve ck{p->d_pk};
     uint32_t* kc = ck.take<uint32_t>((size_t)n * PS_SHARDS);
     int32_t* kcnt = ck.take<int32_t>((size_t)n);
     HIP_OK(hipMemsetAsync(kc, 0, 4 * (size_t)n * PS_SHARDS, s));
     HIP_OK(hipEventRecord(p->ev_m0, s));
-    if (hk) hipLaunchKernelGGL((k_p_walk<true, 2>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, 0, (int)n,
+    if (hk) hipLaunchKernelGGL((k_p_walk<true, 2>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, 0, (int)n,
                                (int32_t*)nullptr, (const int32_t*)nullptr, (uint32_t*)nullptr, (int64_t*)nullptr, 0, kc);
-    else hipLaunchKernelGGL((k_p_walk<false, 2>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, 0, (int)n,
+    else hipLaunchKernelGGL((k_p_walk<false, 2>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, 0, (int)n,
                             (int32_t*)nullptr, (const int32_t*)nullptr, (uint32_t*)nullptr, (int64_t*)nullptr, 0, kc);
     HIP_OK(hipGetLastError());
     hipLaunchKernelGGL(k_p_kfold, dim3((unsigned)((n + P_THREADS - 1) / P_THREADS)), dim3(P_THREADS), 0, s, kc, n, kcnt);
@@ -319,14 +274,14 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
       HIP_OK(hipcub::DeviceScan::ExclusiveSum(nullptr, tmpb, (const int32_t*)pcnt, poff, (int)(S + 1), s));
       // sort arrays are sized below, once M is known; the scan's temporary sits in d_pt until then
       {
-        const int rc = ensure_p(&p->d_pt, &p->pt_bytes, tmpb);
+        const int rc = ensure_scratch(&p->d_pt, &p->pt_bytes, tmpb);
         if (rc) return rc;
       }
       HIP_OK(hipEventRecord(p->ev_m0, s));
-      if (hk) hipLaunchKernelGGL((k_p_walk<true, 0>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, (int)kr.k0,
+      if (hk) hipLaunchKernelGGL((k_p_walk<true, 0>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, (int)kr.k0,
                                  (int)kr.k1, pcnt, (const int32_t*)nullptr, (uint32_t*)nullptr, (int64_t*)nullptr, 0,
                                  (uint32_t*)nullptr);
-      else hipLaunchKernelGGL((k_p_walk<false, 0>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, (int)kr.k0,
+      else hipLaunchKernelGGL((k_p_walk<false, 0>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, (int)kr.k0,
                               (int)kr.k1, pcnt, (const int32_t*)nullptr, (uint32_t*)nullptr, (int64_t*)nullptr, 0,
                               (uint32_t*)nullptr);
       HIP_OK(hipGetLastError());
@@ -348,7 +303,7 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
     {
       const size_t need = 2 * rnd256(4 * Mx) + 2 * rnd256(8 * Mx) + 2 * rnd256(4 * nh) + rnd256(scanb) +
                           rnd256(4 * (size_t)(nk + 1)) * (host_plan ? 1 : 7) + rnd256(kscanb);
-      const int rc = ensure_p(&p->d_ps, &p->ps_bytes, need);
+      const int rc = ensure_scratch(&p->d_ps, &p->ps_bytes, need);
       if (rc) return rc;
     }
     Carve cs{p->d_ps};
@@ -366,9 +321,9 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
     int cur = 0;
     HIP_OK(hipEventRecord(p->ev_m0, s));
     if (M > 0) {
-      if (hk) hipLaunchKernelGGL((k_p_walk<true, 1>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, (int)kr.k0,
+      if (hk) hipLaunchKernelGGL((k_p_walk<true, 1>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, (int)kr.k0,
                                  (int)kr.k1, (int32_t*)nullptr, (const int32_t*)poff, kbuf[0], vbuf[0], M, (uint32_t*)nullptr);
-      else hipLaunchKernelGGL((k_p_walk<false, 1>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, c.a, lgG, ngrp, (int)kr.k0,
+      else hipLaunchKernelGGL((k_p_walk<false, 1>), dim3(wgrid), dim3(P_THREADS), 0, s, c.slab, a, lgG, ngrp, (int)kr.k0,
                               (int)kr.k1, (int32_t*)nullptr, (const int32_t*)poff, kbuf[0], vbuf[0], M, (uint32_t*)nullptr);
       HIP_OK(hipGetLastError());
       // ---- stable sort by key - k0 < nk, 8 bits per pass
@@ -423,7 +378,7 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
       const size_t need = rnd256(sizeof(PTask) * (size_t)std::max<int64_t>(nt, 1)) +
                           rnd256(sizeof(PFold) * (size_t)std::max<int64_t>(nf, 1)) +
                           rnd256(8 * (size_t)std::max<int64_t>(nparts, 1) * (size_t)ldp);
-      const int rc = ensure_p(&p->d_pt, &p->pt_bytes, need);
+      const int rc = ensure_scratch(&p->d_pt, &p->pt_bytes, need);
       if (rc) return rc;
     }
     Carve ct{p->d_pt};
@@ -446,12 +401,12 @@ extern "C" int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, i
       const dim3 grid((unsigned)((nt + P_WPB - 1) / P_WPB), (unsigned)((c1 - c0 + tile - 1) / tile));
       const int64_t* vals = vbuf[cur];
       if (dt == PPR_PROP_F32) {
-        if (V == 4) launch_tsum<0, 4>(c, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
-        else launch_tsum<0, 1>(c, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
+        if (V == 4) launch_tsum<0, 4>(c, a, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
+        else launch_tsum<0, 1>(c, a, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
       } else {
-        if (V == 8) launch_tsum<1, 8>(c, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
-        else if (V == 4) launch_tsum<1, 4>(c, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
-        else launch_tsum<1, 1>(c, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
+        if (V == 8) launch_tsum<1, 8>(c, a, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
+        else if (V == 4) launch_tsum<1, 4>(c, a, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
+        else launch_tsum<1, 1>(c, a, grid, wpos, d_tasks, nt, vals, M, Gm, ldg, Y, ldy, parts, nparts, ldp, c0, c1);
       }
       HIP_OK(hipGetLastError());
       if (nf) {

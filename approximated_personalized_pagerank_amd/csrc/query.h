@@ -24,8 +24,10 @@
 //   k_q_final   one wave per split query: top-Kq of its list
 // The result depends only on the slab and the query: every tier computes the same exact totals and
 // the same total order decides every cut.
+// The helpers shared with the reverse queries and the propagation (slot, length, id decode, the
+// read-only table probe, select-and-compact, the result row) are in resident.h.
 #pragma once
-#include "xs_table.h"
+#include "resident.h"
 
 namespace pprk {
 
@@ -67,12 +69,6 @@ struct QLists {          // appended top-Kq of the range groups, one list per sp
 __host__ __device__ constexpr size_t q_wave_lds(int T) { return (size_t)T * 16 + 1024; }
 __host__ __device__ constexpr size_t q_final_lds(int Kp) { return (size_t)Kp * 12 + 1024; }
 
-__device__ __forceinline__ int q_slot(const QArgs& qa, int u) { return qa.part[u] ? qa.sB : qa.sA; }
-__device__ __forceinline__ int q_len(const DevSlab& s, int slot, int u) {
-  const int len = s.len[s.lrow(slot, u)];
-  return len < 0 ? 0 : len > s.L ? s.L : len;
-}
-
 // Add the segments [range r0, range r1) of the rows of seeds [sb, se) into the table. Wave wv of nw
 // takes every nw-th window of 64 seeds: lane l holds seed l's segment start, length and factor, a
 // scan of the lengths numbers the window's candidates, and every lane finds the seed of its
@@ -90,8 +86,8 @@ __device__ __forceinline__ bool q_accumulate(const DevSlab& s, const QArgs& qa, 
     double f = 0.0;
     if (i < se) {
       const int u = qa.seeds[i];
-      const int slot = q_slot(qa, u);
-      const int len = q_len(s, slot, u);
+      const int slot = res_slot(qa.part, qa.sA, qa.sB, u);
+      const int len = res_len(s, slot, u);
       int b = 0, e = len;
       if (r0 > 0) b = min((int)s.rix[s.xrow(slot, u) + r0 - 1], len);
       if (r1 < NRANGE) e = min((int)s.rix[s.xrow(slot, u) + r1 - 1], len);
@@ -116,12 +112,12 @@ __device__ __forceinline__ bool q_accumulate(const DevSlab& s, const QArgs& qa, 
       if (c < total) {
         const int64_t a = (int64_t)st0 + (c - ex);
         const int32_t id = s.ids[a];
-        // stored id -> key (hot-tagged ids exist after a chain-mode run)
-        const int key = id >= 0 ? id : ((int)((uint32_t)id & 0x7fffffffu) < s.hn ? s.hkeys[(uint32_t)id & 0x7fffffffu] : -1);
+        const int key = res_key<true>(s, id);  // (hot-tagged ids exist after a chain-mode run)
         const double p = s.sc[a] * ft;  // a lone multiply: nothing to contract with
         unsigned long long lo;
         uint32_t hi;
         xs_conv(p, lo, hi);
+        // (key < 0, written as res_key's own compare: one instruction for both)
         if ((uint32_t)key >= (uint32_t)s.n || xt_add(t, key, lo, hi) < 0) bad = true;
       }
     }
@@ -130,22 +126,12 @@ __device__ __forceinline__ bool q_accumulate(const DevSlab& s, const QArgs& qa, 
 }
 
 // PPR_QUERY_EXCLUDE_SEEDS: every seed's slot (if the key is in the table) gets the high word
-// 0xffffffff -- no total reaches it (X < 2^95) -- and q_select drops such slots. Read-only probes:
-// slots are never freed, so a group with an empty slot and no match ends the search.
+// 0xffffffff -- no total reaches it (X < 2^95) -- and q_select drops such slots.
 constexpr uint32_t Q_DROPPED = 0xffffffffu;
 __device__ __forceinline__ void q_exclude(const XTable& t, const QArgs& qa, int64_t sb, int64_t se, int tid, int nthr) {
-  const uint32_t groups = (t.mask + 1u) >> 2;
   for (int64_t i = sb + tid; i < se; i += nthr) {
-    const int key = qa.seeds[i];
-    const uint32_t tag = (uint32_t)key + 1u;
-    uint32_t g = hash32((uint32_t)key) & t.mask & ~3u;
-    for (uint32_t mv = 0; mv < groups; mv++) {
-      const uint4 q = *reinterpret_cast<const uint4*>(t.keys + g);
-      const int m = xt_match(q, g, tag);
-      if (m >= 0) { t.hi[m] = Q_DROPPED; break; }
-      if (q.x == 0u || q.y == 0u || q.z == 0u || q.w == 0u) break;
-      g = (g + 4u) & t.mask;
-    }
+    const int m = res_find(t.keys, t.mask, qa.seeds[i]);
+    if (m >= 0) t.hi[m] = Q_DROPPED;
   }
 }
 
@@ -191,18 +177,6 @@ __device__ __forceinline__ int q_select(const XTable& t, int T, int Kq, uint32_t
   return U2 < Kq ? U2 : Kq;
 }
 
-// One wave: the result row of chunk query q from cnt entries in rv / rk (LDS, room for the next
-// power of two >= cnt, at most cap): sorted (score desc, id asc), unused slots id -1 / score 0.
-__device__ __forceinline__ void q_write_row(const QArgs& qa, int64_t q, uint64_t* rv, int* rk, int cnt, int cap) {
-  row_sort(rv, rk, cnt, cap);
-  const int64_t o = q * (int64_t)qa.Kq;
-  for (int i = lane_id(); i < qa.Kq; i += WAVE) {
-    qa.out_ids[o + i] = i < cnt ? rk[i] : -1;
-    qa.out_sc[o + i] = i < cnt ? bitsd(rv[i]) : 0.0;
-  }
-  if (lane_id() == 0) qa.out_len[q] = cnt;
-}
-
 __device__ __forceinline__ long long q_wave_sum64(long long x) {
 #pragma unroll
   for (int o = 32; o; o >>= 1) x += __shfl_xor(x, o);
@@ -223,8 +197,8 @@ __global__ void __launch_bounds__(Q_WPB * WAVE) k_q_plan(DevSlab s, QArgs qa, in
     long long xr = 0;
     if (i < se) {
       const int u = qa.seeds[i];
-      const int slot = q_slot(qa, u);
-      len = q_len(s, slot, u);
+      const int slot = res_slot(qa.part, qa.sA, qa.sB, u);
+      len = res_len(s, slot, u);
       xr = s.xrow(slot, u);
     }
     C += len;
@@ -280,7 +254,8 @@ __global__ void __launch_bounds__(Q_WPB * WAVE) k_q_wave(DevSlab s, QArgs qa, co
   if (__ballot(bad) && lane_id() == 0) probe_fail();
   if (qa.exclude) { q_exclude(t, qa, sb, se, lane_id(), WAVE); wave_fence(); }
   const int cnt = q_select(t, T, qa.Kq, hist);
-  q_write_row(qa, q, reinterpret_cast<uint64_t*>(t.lo), reinterpret_cast<int*>(t.keys), cnt, T);
+  write_result_row(qa.out_ids, qa.out_sc, qa.out_len, q, qa.Kq, reinterpret_cast<uint64_t*>(t.lo),
+                   reinterpret_cast<int*>(t.keys), cnt, T);
 }
 
 // shared body of k_q_wg / k_q_range: the whole workgroup clears and fills the table, wave 0
@@ -305,7 +280,8 @@ __global__ void __launch_bounds__(Q_WG_THREADS) k_q_wg(DevSlab s, QArgs qa, cons
   uint32_t* hist = reinterpret_cast<uint32_t*>(smem + xt_bytes(T));
   const int cnt = q_wg_merge(s, qa, qa.qptr[q], qa.qptr[q + 1], 0, NRANGE, t, T, hist);
   if (cnt < 0) return;
-  q_write_row(qa, q, reinterpret_cast<uint64_t*>(t.lo), reinterpret_cast<int*>(t.keys), cnt, T);
+  write_result_row(qa.out_ids, qa.out_sc, qa.out_len, q, qa.Kq, reinterpret_cast<uint64_t*>(t.lo),
+                   reinterpret_cast<int*>(t.keys), cnt, T);
 }
 
 __global__ void __launch_bounds__(Q_WG_THREADS) k_q_range(DevSlab s, QArgs qa, const QTask* tasks, int T, QLists ql) {
@@ -340,29 +316,10 @@ __global__ void __launch_bounds__(WAVE) k_q_final(QArgs qa, const int32_t* rqq, 
   const int n = ql.cnt[rq] < cap ? ql.cnt[rq] : (int)cap;
   const int32_t* lk = ql.k + o;
   const double* lv = ql.v + o;
-  int cnt;
-  if (n <= qa.Kq) {
-    for (int i = lane_id(); i < n; i += WAVE) { rv[i] = dbits(lv[i]); rk[i] = lk[i]; }
-    cnt = n;
-  } else {
-    const SelCrit c = select_top(n, qa.Kq, [&](int i) { return lk[i]; }, [&](int i) { return lv[i]; }, hist, 0u,
-                                 TieIdAsc{});
-    int base = 0;
-    for (int i0 = 0; i0 < n; i0 += WAVE) {
-      const int i = i0 + lane_id();
-      bool sel = false;
-      uint64_t vb = 0;
-      int key = 0;
-      if (i < n) { key = lk[i]; vb = dbits(lv[i]); sel = sel_test(c, vb, TieIdAsc{}(key, 0u)); }
-      const uint64_t m = __ballot(sel);
-      const int pos = base + __popcll(m & lanemask_lt());
-      if (sel && pos < qa.Kq) { rv[pos] = vb; rk[pos] = key; }
-      base += __popcll(m);
-    }
-    cnt = base < qa.Kq ? base : qa.Kq;
-  }
+  const int cnt = wave_select_compact(n, qa.Kq, [&](int i) { return lk[i]; }, [&](int i) { return lv[i]; }, hist,
+                                      [&](int pos, int key, uint64_t vb) { rv[pos] = vb; rk[pos] = key; });
   wave_fence();
-  q_write_row(qa, rqq[rq], rv, rk, cnt, Kp);
+  write_result_row(qa.out_ids, qa.out_sc, qa.out_len, rqq[rq], qa.Kq, rv, rk, cnt, Kp);
 }
 
 }  // namespace pprk

@@ -9,50 +9,21 @@
 // chunk (k_q_plan) and refuses the call with PPR_ERR_RANGE if a query is too wide for the range
 // tier -- before any merge kernel starts; phase B merges chunk by chunk. A query's result does not
 // depend on its chunk, its tier or its place in the call.
+// The argument checks and the factors are resident_args.h's, the scratch, timing and probe-error
+// plumbing resident_call.h's; both are shared with rquery.hip and propagate.hip.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <vector>
 
-#include "plan.h"
+#include "resident_call.h"
 #include "query.h"
 
 namespace {
 
 constexpr int64_t Q_CHUNK_DEFAULT = 1 << 18, Q_CHUNK_SEEDS = 1 << 22, Q_CHUNK_OUT = 1 << 24;
 constexpr int64_t Q_BATCH_ENTRIES = 1 << 24, Q_BATCH_TASKS = 1 << 20;
-
-size_t rnd256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(base + off);
-    off += rnd256(n * sizeof(T));
-    return r;
-  }
-};
-
-// grow-only device buffer
-int ensure_q(unsigned char** ptr, size_t* cap, size_t need) {
-  if (need <= *cap) return PPR_OK;
-  if (*ptr) hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  need += need / 4 + 4096;
-  if (hipMalloc((void**)ptr, need) != hipSuccess) return PPR_ERR_OOM;
-  *cap = need;
-  return PPR_OK;
-}
-
-int64_t env_i64(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
 
 // device arrays of one chunk (nq queries, ns seeds), carved from ppr_plan::d_q
 struct ChunkDev {
@@ -81,13 +52,6 @@ struct ChunkDev {
   }
 };
 
-int set_lds(const void* fn, size_t lds) {
-  if (lds <= 64 * 1024) return PPR_OK;
-  if (lds > 160 * 1024) return PPR_ERR_RANGE;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? PPR_OK
-                                                                                                       : PPR_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t Q, const int64_t* qptr,
@@ -95,31 +59,15 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
                                     int32_t* out_ids, double* out_scores, int32_t* out_len, ppr_query_stats* st) {
   if (st) std::memset(st, 0, sizeof(*st));
   // ---- every refusal is decided here, on the host, before any kernel is launched
-  if (!p || p->mc || iterations_run < 0 || Q < 0 || !qptr) return PPR_ERR_ARG;
-  if (Q > 0 && (!out_ids || !out_scores || !out_len)) return PPR_ERR_ARG;
-  if (flags & ~(uint32_t)PPR_QUERY_EXCLUDE_SEEDS) return PPR_ERR_ARG;
-  if (Kq == 0) return PPR_ERR_K;
-  if (Kq > (uint32_t)Q_MAX_K) return PPR_ERR_RANGE;
-  if (qptr[0] != 0) return PPR_ERR_ARG;
-  for (int64_t q = 0; q < Q; q++)
-    if (qptr[q + 1] < qptr[q]) return PPR_ERR_ARG;
-  const int64_t NS = qptr[Q];
-  if (NS > 0 && !seeds) return PPR_ERR_ARG;
-  for (int64_t i = 0; i < NS; i++)
-    if (seeds[i] < 0 || (int64_t)seeds[i] >= p->n) return PPR_ERR_SOURCE;
-  std::vector<double> fac((size_t)std::max<int64_t>(NS, 1));
-  for (int64_t q = 0; q < Q; q++) {
-    const int64_t b = qptr[q], e = qptr[q + 1];
-    double W = 0.0;
-    for (int64_t i = b; i < e; i++) {
-      const double w = weights ? weights[i] : 1.0;
-      if (!(w >= 0.0) || !std::isfinite(w)) return PPR_ERR_ARG;  // negative, NaN, infinite
-      W += w;  // in seed order
-    }
-    if (e > b && (!(W > 0.0) || !std::isfinite(W))) return PPR_ERR_ARG;
-    for (int64_t i = b; i < e; i++) fac[i] = (weights ? weights[i] : 1.0) / W;
+  std::vector<double> fac;  // f_i = w_i / W, W summed in seed order
+  {
+    const int rc = pprres::check_weighted_sets(p && !p->mc && iterations_run >= 0, p ? p->n : 0, Q, qptr, seeds, weights,
+                                               out_ids && out_scores && out_len, Kq, Q_MAX_K,
+                                               flags, PPR_QUERY_EXCLUDE_SEEDS, fac);
+    if (rc) return rc;
   }
   if (Q == 0) return PPR_OK;
+  const int64_t NS = qptr[Q];
 
   // test knobs, read per call
   const int wave_max = (int)std::max<int64_t>(0, std::min<int64_t>(3 * (Q_MIN_T << (Q_WAVE_CLASSES - 1)) / 4,
@@ -127,13 +75,15 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
   const int T = std::max(Q_MIN_T, std::min(Q_MAX_T, pow2_at_least(env_i64("PPR_Q_T", Q_MAX_T))));
   const int64_t chunk_q = std::max<int64_t>(1, env_i64("PPR_Q_CHUNK", Q_CHUNK_DEFAULT));
 
-  HIP_OK(hipSetDevice(p->device));
-  hipStream_t s = p->stream;
-  const DevSlab slab = dev_slab(p);
-  const int sA = ((iterations_run + 1) / 2) & 1, sB = (iterations_run / 2) & 1;
+  ResidentCall call;
+  {
+    const int rc = call.begin(p, iterations_run);
+    if (rc) return rc;
+  }
+  hipStream_t s = call.s;
+  const DevSlab& slab = call.slab;
   const int64_t K = Kq;
-  int Kp = 1;
-  while (Kp < (int)Kq) Kp <<= 1;
+  const int Kp = pprres::pow2_at_least_k(Kq);
 
   // chunk boundaries
   std::vector<int64_t> cb{0};
@@ -149,7 +99,7 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
   auto upload = [&](int64_t q0, int64_t q1, ChunkDev* store) -> int {
     const int64_t nq = q1 - q0, ns = qptr[q1] - qptr[q0];
     const size_t need = ChunkDev(nullptr, nq, ns, K).bytes;
-    const int rc = ensure_q(&p->d_q, &p->q_bytes, need);
+    const int rc = ensure_scratch(&p->d_q, &p->q_bytes, need);
     if (rc) return rc;
     *store = ChunkDev(p->d_q, nq, ns, K);
     rel.resize(nq + 1);
@@ -165,18 +115,9 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
   auto qargs = [&](const ChunkDev& d) {
     QArgs a;
     a.qptr = d.qptr; a.seeds = d.seeds; a.fac = d.fac; a.part = p->d_part;
-    a.sA = sA; a.sB = sB; a.Kq = (int)Kq; a.exclude = flags & PPR_QUERY_EXCLUDE_SEEDS;
+    a.sA = call.sA; a.sB = call.sB; a.Kq = (int)Kq; a.exclude = flags & PPR_QUERY_EXCLUDE_SEEDS;
     a.out_ids = d.out_ids; a.out_sc = d.out_sc; a.out_len = d.out_len;
     return a;
-  };
-  double dev_ms = 0.0;
-  auto lap = [&]() -> int {  // kernels between ev_m0 and ev_m1 (waits for them)
-    HIP_OK(hipEventRecord(p->ev_m1, s));
-    HIP_OK(hipEventSynchronize(p->ev_m1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, p->ev_m0, p->ev_m1));
-    dev_ms += ms;
-    return PPR_OK;
   };
 
   // ---- phase A: plan every chunk
@@ -191,7 +132,7 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
     hipLaunchKernelGGL(k_q_plan, dim3((unsigned)((nq + Q_WPB - 1) / Q_WPB)), dim3(Q_WPB * WAVE), 0, s, slab, qargs(cd),
                        nq, wave_max, T, cd.code, cd.cand);
     HIP_OK(hipGetLastError());
-    rc = lap();
+    rc = call.lap();
     if (rc) return rc;
     HIP_OK(hipMemcpyAsync(code.data() + q0, cd.code, 4 * (size_t)nq, hipMemcpyDeviceToHost, s));
     HIP_OK(hipMemcpyAsync(cand.data() + q0, cd.cand, 8 * (size_t)nq, hipMemcpyDeviceToHost, s));
@@ -271,7 +212,7 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
       i = b.rq1;
     }
     if (ql_need) {
-      const int rc = ensure_q(&p->d_ql, &p->ql_bytes, ql_need);
+      const int rc = ensure_scratch(&p->d_ql, &p->ql_bytes, ql_need);
       if (rc) return rc;
     }
     const QArgs qa = qargs(cd);
@@ -291,7 +232,7 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
         HIP_OK(hipGetLastError());
       }
     {
-      const int rc = lap();
+      const int rc = call.lap();
       if (rc) return rc;
     }
     std::vector<int64_t> boff;
@@ -316,7 +257,7 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
       HIP_OK(hipGetLastError());
       hipLaunchKernelGGL(k_q_final, dim3((unsigned)nb), dim3(WAVE), q_final_lds(Kp), s, qa, cd.list + r0 + b.rq0, ql, Kp);
       HIP_OK(hipGetLastError());
-      const int rc = lap();
+      const int rc = call.lap();
       if (rc) return rc;
     }
     HIP_OK(hipMemcpyAsync(out_ids + q0 * K, cd.out_ids, 4 * (size_t)(nq * K), hipMemcpyDeviceToHost, s));
@@ -325,15 +266,12 @@ extern "C" int ppr_grank_plan_query(ppr_plan* p, int32_t iterations_run, int64_t
     HIP_OK(hipStreamSynchronize(s));
   }
   // a bounded probe that ran out (a sizing error: the planner rules it out)
-  unsigned int bad = 0u;
-  HIP_OK(hipMemcpyFromSymbol(&bad, HIP_SYMBOL(g_probe_err), sizeof(bad), 0, hipMemcpyDeviceToHost));
-  if (bad) {
-    const unsigned int z = 0u;
-    HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_err), &z, sizeof(z), 0, hipMemcpyHostToDevice));
-    return PPR_ERR_PROBE;
+  {
+    const int rc = take_probe_err();
+    if (rc) return rc;
   }
   if (st) {
-    st->device_ms = dev_ms;
+    st->device_ms = call.dev_ms;
     st->candidates = C;
     st->algo_bytes = 8 * NS + 12 * C + Q * (12 * K + 4);
     st->wave_queries = nwave;

@@ -35,8 +35,10 @@
 //                   chunk) <= 3/4 of its slots.
 // A probe that runs out anyway sets g_probe_err (PPR_ERR_PROBE). Every tier computes the same exact
 // totals and one total order decides every cut: the result depends only on the slab and the query.
+// The helpers shared with the forward queries and the propagation (slot, length, id decode, the
+// read-only table probe, select-and-compact, the result row) are in resident.h.
 #pragma once
-#include "xs_table.h"
+#include "resident.h"
 
 namespace pprk {
 
@@ -99,44 +101,16 @@ __host__ __device__ constexpr size_t r_scan_lds(int Tt) {
 }
 __host__ __device__ constexpr size_t r_final_lds(int Kp) { return (size_t)Kp * 12 + 1024; }
 
-__device__ __forceinline__ int r_slot(const RArgs& a, int64_t u) { return a.part[u] ? a.sB : a.sA; }
-__device__ __forceinline__ int r_len(const DevSlab& s, int slot, int64_t u) {  // (q_len's clamp)
-  const int len = s.len[s.lrow(slot, u)];
-  return len < 0 ? 0 : len > s.L ? s.L : len;
-}
-// stored id -> key, -1 for an id no key stands behind (hot-tagged ids exist after a chain-mode run)
-__device__ __forceinline__ int r_key(const DevSlab& s, int32_t id) {
-  if (id >= 0) return (int64_t)id < s.n ? id : -1;
-  const uint32_t h = (uint32_t)id & 0x7fffffffu;
-  return (int)h < s.hn ? s.hkeys[h] : -1;
-}
-
-// index of the distinct target `key` (in [0, n)) or -1. Read-only: the image is never more than 3/4
-// full, so a group with an empty slot and no match ends the search.
+// index of the distinct target `key` (in [0, n)) or -1: the image is never more than 3/4 full
 __device__ __forceinline__ int r_lookup(const uint32_t* tk, const uint32_t* tv, int Tt, int key) {
-  const uint32_t tag = (uint32_t)key + 1u, mask = (uint32_t)Tt - 1u;
-  uint32_t g = hash32((uint32_t)key) & mask & ~3u;
-  for (uint32_t mv = 0; mv < ((uint32_t)Tt >> 2); mv++) {
-    const uint4 q = *reinterpret_cast<const uint4*>(tk + g);
-    const int m = xt_match(q, g, tag);
-    if (m >= 0) return (int)tv[m];
-    if (q.x == 0u || q.y == 0u || q.z == 0u || q.w == 0u) return -1;
-    g = (g + 4u) & mask;
-  }
-  return -1;
+  const int m = res_find(tk, (uint32_t)Tt - 1u, key);
+  return m >= 0 ? (int)tv[m] : -1;
 }
 
 // mark query q of the table dropped (its source is one of its targets)
 __device__ __forceinline__ void r_drop(const XTable& t, int q) {
-  const uint32_t tag = (uint32_t)q + 1u;
-  uint32_t g = hash32((uint32_t)q) & t.mask & ~3u;
-  for (uint32_t mv = 0; mv < ((t.mask + 1u) >> 2); mv++) {
-    const uint4 k = *reinterpret_cast<const uint4*>(t.keys + g);
-    const int m = xt_match(k, g, tag);
-    if (m >= 0) { t.hi[m] = R_DROPPED; return; }
-    if (k.x == 0u || k.y == 0u || k.z == 0u || k.w == 0u) return;
-    g = (g + 4u) & t.mask;
-  }
+  const int m = res_find(t.keys, t.mask, q);
+  if (m >= 0) t.hi[m] = R_DROPPED;
 }
 
 // one (query, source) hit: counted, or appended to the query's list (any order: the final order is total)
@@ -243,8 +217,8 @@ __global__ void __launch_bounds__(R_SCAN_THREADS) k_r_scan(DevSlab s, RArgs a, i
     int len = 0;
     int64_t row = 0;
     if (u < s.n) {
-      const int slot = r_slot(a, u);
-      len = r_len(s, slot, u);
+      const int slot = res_slot(a.part, a.sA, a.sB, u);
+      len = res_len(s, slot, u);
       row = s.row(slot, u);
     }
     if (!EMIT && j == 0) lensum += (unsigned long long)len;
@@ -268,7 +242,7 @@ __global__ void __launch_bounds__(R_SCAN_THREADS) k_r_scan(DevSlab s, RArgs a, i
 #pragma unroll
         for (int k = 0; k < V; k++) {
           if (c + k < len) {
-            const int key = r_key(s, id[k]);
+            const int key = res_key<true>(s, id[k]);
             if (key >= 0) hv[k] = r_lookup(tk, tv, a.Tt, key);
           }
         }
@@ -320,12 +294,12 @@ __global__ void __launch_bounds__(R_OVF_THREADS) k_r_ovf(DevSlab s, RArgs a, int
   const int u = a.ovf[blockIdx.x];
   for (int i = tid; i < T; i += R_OVF_THREADS) { t.keys[i] = 0u; t.lo[i] = 0ull; t.hi[i] = 0u; }
   __syncthreads();
-  const int slot = r_slot(a, u);
-  const int len = r_len(s, slot, u);
+  const int slot = res_slot(a.part, a.sA, a.sB, u);
+  const int len = res_len(s, slot, u);
   const int64_t row = s.row(slot, u);
   bool bad = false;
   for (int c = tid; c < len; c += R_OVF_THREADS) {
-    const int key = r_key(s, s.ids[row + c]);
+    const int key = res_key<true>(s, s.ids[row + c]);
     const int d = key >= 0 ? r_lookup(a.tkeys, a.tvals, a.Tt, key) : -1;
     if (d < 0) continue;
     const double sv = EMIT ? s.sc[row + c] : 0.0;
@@ -361,8 +335,8 @@ __global__ void __launch_bounds__(R_PROBE_THREADS) k_r_probe(DevSlab s, RArgs a)
   int len = 0;
   int64_t row = 0, xr = 0;
   if (live) {
-    const int slot = r_slot(a, u);
-    len = r_len(s, slot, u);
+    const int slot = res_slot(a.part, a.sA, a.sB, u);
+    len = res_len(s, slot, u);
     row = s.row(slot, u);
     xr = s.xrow(slot, u);
   }
@@ -382,7 +356,7 @@ __global__ void __launch_bounds__(R_PROBE_THREADS) k_r_probe(DevSlab s, RArgs a)
       const int e = rg < NRANGE - 1 ? min((int)s.rix[xr + rg], len) : len;
       segs += (unsigned long long)(e > b ? e - b : 0);
       for (int c = b; c < e; c++) {
-        if (r_key(s, s.ids[row + c]) != t) continue;
+        if (res_key<true>(s, s.ids[row + c]) != t) continue;
         unsigned long long xl;
         uint32_t xh;
         xs_conv(s.sc[row + c] * a.fac[j], xl, xh);  // a lone multiply
@@ -421,27 +395,12 @@ __global__ void __launch_bounds__(R_WPB * WAVE) k_r_seg(const RSeg* tasks, int64
   const double* iv = lv + tk.in_off;
   int32_t* ok = lk + tk.out_off;
   double* ov = lv + tk.out_off;
-  if (n <= Kq) {
-    for (int i = lane_id(); i < n; i += WAVE) { ok[i] = ik[i]; ov[i] = iv[i]; }
-    return;
-  }
-  const SelCrit c = select_top(n, Kq, [&](int i) { return ik[i]; }, [&](int i) { return iv[i]; }, hist, 0u, TieIdAsc{});
-  int base = 0;
-  for (int i0 = 0; i0 < n; i0 += WAVE) {
-    const int i = i0 + lane_id();
-    bool sel = false;
-    double x = 0.0;
-    int key = 0;
-    if (i < n) { key = ik[i]; x = iv[i]; sel = sel_test(c, dbits(x), TieIdAsc{}(key, 0u)); }
-    const uint64_t m = __ballot(sel);
-    const int pos = base + __popcll(m & lanemask_lt());
-    if (sel && pos < Kq) { ok[pos] = key; ov[pos] = x; }
-    base += __popcll(m);
-  }
+  wave_select_compact(n, Kq, [&](int i) { return ik[i]; }, [&](int i) { return iv[i]; }, hist,
+                      [&](int pos, int key, uint64_t vb) { ok[pos] = key; ov[pos] = bitsd(vb); });
 }
 
 // One wave per query: the top-Kq of its (reduced) list, sorted (score desc, id asc), unused slots
-// id -1 / score 0 (q_write_row's layout).
+// id -1 / score 0 (write_result_row).
 __global__ void __launch_bounds__(WAVE) k_r_final(const RSeg* tasks, const int32_t* lk, const double* lv, int Kq, int Kp,
                                                   int32_t* out_ids, double* out_sc, int32_t* out_len) {
   extern __shared__ __align__(16) unsigned char smem[];
@@ -452,34 +411,10 @@ __global__ void __launch_bounds__(WAVE) k_r_final(const RSeg* tasks, const int32
   const int n = tk.n;
   const int32_t* ik = lk + tk.in_off;
   const double* iv = lv + tk.in_off;
-  int cnt;
-  if (n <= Kq) {
-    for (int i = lane_id(); i < n; i += WAVE) { rv[i] = dbits(iv[i]); rk[i] = ik[i]; }
-    cnt = n;
-  } else {
-    const SelCrit c = select_top(n, Kq, [&](int i) { return ik[i]; }, [&](int i) { return iv[i]; }, hist, 0u, TieIdAsc{});
-    int base = 0;
-    for (int i0 = 0; i0 < n; i0 += WAVE) {
-      const int i = i0 + lane_id();
-      bool sel = false;
-      uint64_t vb = 0;
-      int key = 0;
-      if (i < n) { key = ik[i]; vb = dbits(iv[i]); sel = sel_test(c, vb, TieIdAsc{}(key, 0u)); }
-      const uint64_t m = __ballot(sel);
-      const int pos = base + __popcll(m & lanemask_lt());
-      if (sel && pos < Kq) { rv[pos] = vb; rk[pos] = key; }
-      base += __popcll(m);
-    }
-    cnt = base < Kq ? base : Kq;
-  }
+  const int cnt = wave_select_compact(n, Kq, [&](int i) { return ik[i]; }, [&](int i) { return iv[i]; }, hist,
+                                      [&](int pos, int key, uint64_t vb) { rv[pos] = vb; rk[pos] = key; });
   wave_fence();
-  row_sort(rv, rk, cnt, Kp);
-  const int64_t o = (int64_t)tk.q * Kq;
-  for (int i = lane_id(); i < Kq; i += WAVE) {
-    out_ids[o + i] = i < cnt ? rk[i] : -1;
-    out_sc[o + i] = i < cnt ? bitsd(rv[i]) : 0.0;
-  }
-  if (lane_id() == 0) out_len[tk.q] = cnt;
+  write_result_row(out_ids, out_sc, out_len, tk.q, Kq, rv, rk, cnt, Kp);
 }
 
 }  // namespace pprk

@@ -18,56 +18,23 @@
 // lists. A separate count pass was kept: it reads no score, and it is what bounds the list memory at
 // 12 E bytes for any hit counts -- a single pass with worst-case lists would need 12 n bytes per
 // query. The reduction levels append at most as many entries again (a segment holds >= 2 Kq).
+// The argument checks and the factors are resident_args.h's, the scratch, timing and probe-error
+// plumbing resident_call.h's (shared with query.hip and propagate.hip); the table image is built
+// with the hash32 the kernels probe it with (hash32.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cmath>
 #include <cstring>
 #include <numeric>
 #include <vector>
 
-#include "plan.h"
+#include "resident_call.h"
 #include "rquery.h"
 
 namespace {
 
 constexpr int64_t R_CHUNK_DEFAULT = 4096, R_CHUNK_OUT = 1 << 24, R_ENTRIES_DEFAULT = 1 << 24;
 constexpr int64_t R_SEG_DEFAULT = 1024, R_PROBE_MAX_DEFAULT = 16;
-
-size_t rnd256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-struct Carve {
-  unsigned char* base;
-  size_t off = 0;
-  template <class T>
-  T* take(size_t n) {
-    T* r = reinterpret_cast<T*>(base + off);
-    off += rnd256(n * sizeof(T));
-    return r;
-  }
-};
-
-// grow-only device buffer
-int ensure_r(unsigned char** ptr, size_t* cap, size_t need) {
-  if (need <= *cap) return PPR_OK;
-  if (*ptr) hipFree(*ptr);
-  *ptr = nullptr;
-  *cap = 0;
-  need += need / 4 + 4096;
-  if (hipMalloc((void**)ptr, need) != hipSuccess) return PPR_ERR_OOM;
-  *cap = need;
-  return PPR_OK;
-}
-
-int64_t env_i64(const char* name, int64_t dflt) {
-  const char* e = getenv(name);
-  return e ? atoll(e) : dflt;
-}
-
-uint32_t h_hash32(uint32_t x) {  // ppr_device.h hash32
-  x ^= x >> 16; x *= 0x7feb352dU; x ^= x >> 15; x *= 0x846ca68bU; x ^= x >> 16;
-  return x;
-}
 
 // device arrays of one chunk (nq queries, np postings), carved from ppr_plan::d_r
 struct RChunkDev {
@@ -113,13 +80,6 @@ struct RChunkDev {
   }
 };
 
-int set_lds(const void* fn, size_t lds) {
-  if (lds <= 64 * 1024) return PPR_OK;
-  if (lds > 160 * 1024) return PPR_ERR_RANGE;
-  return hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess ? PPR_OK
-                                                                                                       : PPR_ERR_HIP;
-}
-
 }  // namespace
 
 extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_t Q, const int64_t* qptr,
@@ -128,29 +88,12 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
                                      ppr_rquery_stats* st) {
   if (st) std::memset(st, 0, sizeof(*st));
   // ---- every refusal is decided here, on the host, before any kernel is launched
-  if (!p || p->mc || iterations_run < 0 || Q < 0 || !qptr) return PPR_ERR_ARG;
-  if (Q > 0 && (!out_sources || !out_scores || !out_len)) return PPR_ERR_ARG;
-  if (flags & ~(uint32_t)PPR_RQUERY_EXCLUDE_TARGETS) return PPR_ERR_ARG;
-  if (Kq == 0) return PPR_ERR_K;
-  if (Kq > (uint32_t)R_MAX_K) return PPR_ERR_RANGE;
-  if (qptr[0] != 0) return PPR_ERR_ARG;
-  for (int64_t q = 0; q < Q; q++)
-    if (qptr[q + 1] < qptr[q]) return PPR_ERR_ARG;
-  const int64_t NP = qptr[Q];
-  if (NP > 0 && !targets) return PPR_ERR_ARG;
-  for (int64_t i = 0; i < NP; i++)
-    if (targets[i] < 0 || (int64_t)targets[i] >= p->n) return PPR_ERR_SOURCE;
-  std::vector<double> fac((size_t)std::max<int64_t>(NP, 1));
-  for (int64_t q = 0; q < Q; q++) {
-    const int64_t b = qptr[q], e = qptr[q + 1];
-    double W = 0.0;
-    for (int64_t i = b; i < e; i++) {
-      const double w = weights ? weights[i] : 1.0;
-      if (!(w >= 0.0) || !std::isfinite(w)) return PPR_ERR_ARG;  // negative, NaN, infinite
-      W += w;  // in target order
-    }
-    if (e > b && (!(W > 0.0) || !std::isfinite(W))) return PPR_ERR_ARG;
-    for (int64_t i = b; i < e; i++) fac[i] = (weights ? weights[i] : 1.0) / W;
+  std::vector<double> fac;  // f_j = w_j / W, W summed in target order
+  {
+    const int rc = pprres::check_weighted_sets(p && !p->mc && iterations_run >= 0, p ? p->n : 0, Q, qptr, targets,
+                                               weights, out_sources && out_scores && out_len, Kq, R_MAX_K, flags,
+                                               PPR_RQUERY_EXCLUDE_TARGETS, fac);
+    if (rc) return rc;
   }
   const int T = std::max(R_MIN_T, std::min(R_MAX_T, pow2_at_least(env_i64("PPR_R_T", R_MAX_T))));
   const int64_t cap = 3 * (int64_t)T / 4;  // postings of a chunk
@@ -164,12 +107,14 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
   const int64_t E = std::max<int64_t>(env_i64("PPR_R_ENTRIES", R_ENTRIES_DEFAULT), n);
   const int64_t SEG = std::min<int64_t>(1 << 30, std::max<int64_t>(env_i64("PPR_R_SEG", R_SEG_DEFAULT), 2 * K));
 
-  HIP_OK(hipSetDevice(p->device));
-  hipStream_t s = p->stream;
-  const DevSlab slab = dev_slab(p);
-  const int sA = ((iterations_run + 1) / 2) & 1, sB = (iterations_run / 2) & 1;
-  int Kp = 1;
-  while (Kp < (int)Kq) Kp <<= 1;
+  ResidentCall call;
+  {
+    const int rc = call.begin(p, iterations_run);
+    if (rc) return rc;
+  }
+  hipStream_t s = call.s;
+  const DevSlab& slab = call.slab;
+  const int Kp = pprres::pow2_at_least_k(Kq);
   // row walk geometry (rquery.h k_r_scan)
   const int V = p->L % 4 == 0 ? 4 : 1;
   int lgG = 0;
@@ -188,16 +133,6 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
     if (!rc) rc = set_lds((const void*)k_r_final, r_final_lds(Kp));
     if (rc) return rc;
   }
-
-  double dev_ms = 0.0;
-  auto lap = [&]() -> int {  // kernels between ev_m0 and ev_m1 (waits for them)
-    HIP_OK(hipEventRecord(p->ev_m1, s));
-    HIP_OK(hipEventSynchronize(p->ev_m1));
-    float ms = 0.f;
-    HIP_OK(hipEventElapsedTime(&ms, p->ev_m0, p->ev_m1));
-    dev_ms += ms;
-    return PPR_OK;
-  };
 
   int64_t tot_hits = 0, probe_queries = 0, scan_queries = 0, scans = 0, nchunks = 0, list_entries = 0;
   int64_t sumlen = -1, probe_bytes = 0;
@@ -241,7 +176,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
   RSeg* d_tasks = nullptr;
   int64_t reserved = 0;
   auto reserve_lists = [&](int64_t entries) -> int {
-    const int rc = ensure_r(&p->d_rl, &p->rl_bytes, rnd256(4 * (size_t)entries) + rnd256(8 * (size_t)entries));
+    const int rc = ensure_scratch(&p->d_rl, &p->rl_bytes, rnd256(4 * (size_t)entries) + rnd256(8 * (size_t)entries));
     if (rc) return rc;
     Carve cv{p->d_rl};
     lk = cv.take<int32_t>(entries);
@@ -250,7 +185,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
     return PPR_OK;
   };
   auto upload_tasks = [&]() -> int {
-    const int rc = ensure_r(&p->d_rt, &p->rt_bytes, sizeof(RSeg) * tasks.size());
+    const int rc = ensure_scratch(&p->d_rt, &p->rt_bytes, sizeof(RSeg) * tasks.size());
     if (rc) return rc;
     d_tasks = reinterpret_cast<RSeg*>(p->d_rt);
     HIP_OK(hipMemcpyAsync(d_tasks, tasks.data(), sizeof(RSeg) * tasks.size(), hipMemcpyHostToDevice, s));
@@ -291,13 +226,13 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
     while (!probe && lgS < R_MAX_LGS && (nq << (lgS + 1)) <= 4096) lgS++;
     const int64_t nc = nq << lgS, S = (int64_t)1 << lgS;
     {
-      const int rc = ensure_r(&p->d_r, &p->r_bytes, RChunkDev(nullptr, nq, np, T, n, K, nc).bytes);
+      const int rc = ensure_scratch(&p->d_r, &p->r_bytes, RChunkDev(nullptr, nq, np, T, n, K, nc).bytes);
       if (rc) return rc;
     }
     const RChunkDev d(p->d_r, nq, np, T, n, K, nc);
     RArgs a;
     std::memset(&a, 0, sizeof(a));
-    a.part = p->d_part; a.sA = sA; a.sB = sB; a.Kq = (int)Kq; a.exclude = flags & PPR_RQUERY_EXCLUDE_TARGETS;
+    a.part = p->d_part; a.sA = call.sA; a.sB = call.sB; a.Kq = (int)Kq; a.exclude = flags & PPR_RQUERY_EXCLUDE_TARGETS;
     a.nq = (int)nq; a.lgS = lgS; a.qptr = d.qptr; a.targets = d.targets; a.fac = d.fac;
     a.tkeys = d.tkeys; a.tvals = d.tvals; a.Tt = 4; a.tptr = d.tptr; a.pq = d.pq; a.pf = d.pf;
     a.hits = d.hits; a.loff = d.loff; a.lcnt = d.lcnt; a.ovf = d.ovf; a.ovf_cnt = d.ovf_cnt; a.stat = d.stat;
@@ -332,7 +267,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
                          s, slab, a);
       HIP_OK(hipGetLastError());
       {
-        const int rc = lap();
+        const int rc = call.lap();
         if (rc) return rc;
       }
       HIP_OK(hipMemcpyAsync(cpad.data(), d.lcnt, 4 * (size_t)(nc * R_CSTRIDE), hipMemcpyDeviceToHost, s));
@@ -370,7 +305,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
       tkeys.assign((size_t)Tt, 0u);
       tvals.assign((size_t)Tt, 0u);
       for (int64_t i = 0; i < D; i++) {
-        uint32_t g = h_hash32((uint32_t)dkey[i]) & (uint32_t)(Tt - 1) & ~3u;
+        uint32_t g = hash32((uint32_t)dkey[i]) & (uint32_t)(Tt - 1) & ~3u;
         for (;;) {  // (ends: the image is at most 3/4 full)
           int e = -1;
           for (int k = 0; k < 4 && e < 0; k++)
@@ -406,7 +341,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
       // ---- count pass
       HIP_OK(hipEventRecord(p->ev_m0, s));
       int rc = scan(false);
-      if (!rc) rc = lap();
+      if (!rc) rc = call.lap();
       if (rc) return rc;
       int32_t novf = 0;
       HIP_OK(hipMemcpyAsync(&novf, d.ovf_cnt, 4, hipMemcpyDeviceToHost, s));
@@ -416,7 +351,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
         HIP_OK(hipEventRecord(p->ev_m0, s));
         hipLaunchKernelGGL((k_r_ovf<false>), dim3((unsigned)novf), dim3(R_OVF_THREADS), xt_bytes(To), s, slab, a, To);
         HIP_OK(hipGetLastError());
-        rc = lap();
+        rc = call.lap();
         if (rc) return rc;
       }
       unsigned long long stat[2] = {0, 0};
@@ -460,7 +395,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
           HIP_OK(hipGetLastError());
         }
         rc = launch_reduce(d);
-        if (!rc) rc = lap();
+        if (!rc) rc = call.lap();
         if (rc) return rc;
         list_entries += used;
         b0 = b1;
@@ -481,7 +416,7 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
       if (rc) return rc;
       HIP_OK(hipEventRecord(p->ev_m0, s));
       rc = launch_reduce(d);
-      if (!rc) rc = lap();
+      if (!rc) rc = call.lap();
       if (rc) return rc;
       for (int64_t i = 0; i < nq; i++) list_entries += hits[i];
     }
@@ -493,15 +428,12 @@ extern "C" int ppr_grank_plan_rquery(ppr_plan* p, int32_t iterations_run, int64_
     q0 = q1;
   }
   // a bounded probe that ran out (a sizing error: the chunking rules it out)
-  unsigned int bad = 0u;
-  HIP_OK(hipMemcpyFromSymbol(&bad, HIP_SYMBOL(g_probe_err), sizeof(bad), 0, hipMemcpyDeviceToHost));
-  if (bad) {
-    const unsigned int z = 0u;
-    HIP_OK(hipMemcpyToSymbol(HIP_SYMBOL(g_probe_err), &z, sizeof(z), 0, hipMemcpyHostToDevice));
-    return PPR_ERR_PROBE;
+  {
+    const int rc = take_probe_err();
+    if (rc) return rc;
   }
   if (st) {
-    st->device_ms = dev_ms;
+    st->device_ms = call.dev_ms;
     st->hits = tot_hits;
     st->algo_bytes = scans * (4 * std::max<int64_t>(sumlen, 0) + 4 * n) + probe_bytes + 32 * list_entries + Q * (12 * K + 4);
     st->probe_queries = probe_queries;

@@ -294,6 +294,20 @@ class GrankPlan:
                    "fetch_slab")
         return ids, sc, lens
 
+    def _resident_query(self, symbol, where, queries, K, weights, flags, iterations_run, st, counters):
+        """the call both query directions make: (ids, scores, lens, device_ms, *the stats' integer counters)"""
+        qptr, ids_in, w = normalize_queries(queries, weights)
+        Q = len(qptr) - 1
+        it = self.iterations_run if iterations_run is None else iterations_run
+        ids = np.full((Q, max(K, 0)), -1, dtype=np.int32)
+        sc = np.zeros((Q, max(K, 0)), dtype=np.float64)
+        lens = np.zeros(Q, dtype=np.int32)
+        if K < 0 or K >= 2**32:
+            raise _lib.PprError(1, where)
+        _lib.check(getattr(_lib.lib(), symbol)(self._p, it, Q, _lib.ptr(qptr), _lib.ptr(ids_in), _lib.ptr(w), K, flags,
+                                               _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens), ctypes.byref(st)), where)
+        return (ids, sc, lens, float(st.device_ms)) + tuple(int(getattr(st, f)) for f in counters)
+
     def query(self, queries, K: int, weights=None, exclude_seeds: bool = False,
               iterations_run: Optional[int] = None) -> QueryResult:
         """PageRank personalised to each query's seed set, from the plan's resident baskets
@@ -301,21 +315,10 @@ class GrankPlan:
         vectors, summed exactly, the K best by (score desc, dense id asc). `queries`: (qptr, seeds)
         arrays or a sequence of seed sequences of dense ids; `weights`: None (all 1), a flat array
         or sequences of the same shape; `iterations_run` defaults to the plan's last run."""
-        qptr, seeds, w = normalize_queries(queries, weights)
-        Q = len(qptr) - 1
-        it = self.iterations_run if iterations_run is None else iterations_run
-        ids = np.full((Q, max(K, 0)), -1, dtype=np.int32)
-        sc = np.zeros((Q, max(K, 0)), dtype=np.float64)
-        lens = np.zeros(Q, dtype=np.int32)
-        st = _lib.PprQueryStats()
-        flags = _lib.PPR_QUERY_EXCLUDE_SEEDS if exclude_seeds else 0
-        if K < 0 or K >= 2**32:
-            raise _lib.PprError(1, "plan_query")
-        _lib.check(_lib.lib().ppr_grank_plan_query(self._p, it, Q, _lib.ptr(qptr), _lib.ptr(seeds), _lib.ptr(w), K,
-                                                   flags, _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens),
-                                                   ctypes.byref(st)), "plan_query")
-        return QueryResult(ids, sc, lens, float(st.device_ms), int(st.candidates), int(st.algo_bytes),
-                           int(st.wave_queries), int(st.wg_queries), int(st.range_queries), int(st.max_ranges))
+        return QueryResult(*self._resident_query("ppr_grank_plan_query", "plan_query", queries, K, weights,
+                                                 _lib.PPR_QUERY_EXCLUDE_SEEDS if exclude_seeds else 0, iterations_run,
+                                                 _lib.PprQueryStats(), ("candidates", "algo_bytes", "wave_queries",
+                                                                        "wg_queries", "range_queries", "max_ranges")))
 
     def rquery(self, queries, K: int, weights=None, exclude_targets: bool = False,
                iterations_run: Optional[int] = None) -> RQueryResult:
@@ -324,21 +327,11 @@ class GrankPlan:
         targets that are keys of u's basket, summed exactly, the K best sources by (score desc,
         dense id asc). Arguments as for query(); `exclude_targets` drops the sources that are
         targets of their query."""
-        qptr, targets, w = normalize_queries(queries, weights)
-        Q = len(qptr) - 1
-        it = self.iterations_run if iterations_run is None else iterations_run
-        ids = np.full((Q, max(K, 0)), -1, dtype=np.int32)
-        sc = np.zeros((Q, max(K, 0)), dtype=np.float64)
-        lens = np.zeros(Q, dtype=np.int32)
-        st = _lib.PprRQueryStats()
-        flags = _lib.PPR_RQUERY_EXCLUDE_TARGETS if exclude_targets else 0
-        if K < 0 or K >= 2**32:
-            raise _lib.PprError(1, "plan_rquery")
-        _lib.check(_lib.lib().ppr_grank_plan_rquery(self._p, it, Q, _lib.ptr(qptr), _lib.ptr(targets), _lib.ptr(w), K,
-                                                    flags, _lib.ptr(ids), _lib.ptr(sc), _lib.ptr(lens),
-                                                    ctypes.byref(st)), "plan_rquery")
-        return RQueryResult(ids, sc, lens, float(st.device_ms), int(st.hits), int(st.algo_bytes),
-                            int(st.probe_queries), int(st.scan_queries), int(st.scans), int(st.chunks))
+        return RQueryResult(*self._resident_query("ppr_grank_plan_rquery", "plan_rquery", queries, K, weights,
+                                                  _lib.PPR_RQUERY_EXCLUDE_TARGETS if exclude_targets else 0,
+                                                  iterations_run, _lib.PprRQueryStats(),
+                                                  ("hits", "algo_bytes", "probe_queries", "scan_queries", "scans",
+                                                   "chunks")))
 
     # ---- feature propagation (include/ppr_hip.h ppr_grank_plan_propagate / _propagate_t) ----
     @property
