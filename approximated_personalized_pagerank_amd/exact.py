@@ -65,6 +65,9 @@ class ExactPPR:
     def gather(self, keys: np.ndarray) -> np.ndarray:
         """scores of keys[s, q] for source s (0 where the source never reached the node)"""
         keys = np.ascontiguousarray(keys, dtype=np.int32)
+        # the library copies len(sources) * Q keys in and as many scores out
+        if keys.ndim != 2 or keys.shape[0] != len(self.sources):
+            raise ValueError(f"keys must be [len(sources) = {len(self.sources)}, Q], got shape {keys.shape}")
         out = np.zeros(keys.shape, dtype=np.float64)
         _lib.check(_lib.lib().ppr_exact_gather(self._h, keys.shape[1], _lib.ptr(keys), _lib.ptr(out)), "exact_gather")
         return out

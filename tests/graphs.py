@@ -6,6 +6,7 @@ returns (row_ptr int64 [n + 1], col int32 [m]) with each successor list in the o
                 successor (candidates far above distinct keys) and the LAST dense id is a wide source
   layered       complete layers: every key of a layer carries the same mass, so a cut falls inside a
                 tie of up to G keys
+  sparse_random out-degree 1..8 with a share of dangling nodes (tests/test_gpu_exact.py)
   rmat_grafted  RMAT plus appended nodes: n is odd, the appended ids close unsorted lists
 """
 import numpy as np
@@ -48,6 +49,16 @@ def layered(G, m, half=False):
             nn = ((v // G + 2) % m) * G
             s.extend(range(nn, nn + G, 2))
         lists.append(s)
+    return _csr(lists)
+
+
+def sparse_random(n, seed, dangling=0.05):
+    """node v: 1 to 8 random successors (repeats and self-loops as they fall); a `dangling` share of
+    the nodes, picked at random, has none"""
+    rng = np.random.default_rng(seed)
+    lists = [rng.integers(0, n, int(rng.integers(1, 9))).tolist() for _ in range(n)]
+    for v in rng.choice(n, max(1, int(round(n * dangling))), replace=False):
+        lists[int(v)] = []
     return _csr(lists)
 
 
