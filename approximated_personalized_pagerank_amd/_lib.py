@@ -21,7 +21,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libppr_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 # every file the library is compiled from (csrc/ plus the public header), in digest order
-CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
+CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "sweep.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
 # every header of csrc/ (a new one can not be left out of the provenance digest) and the C ABI
 CSRC_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "ppr_hip.h")]
 
@@ -160,6 +160,19 @@ class PprPropStats(ctypes.Structure):
     ]
 
 
+class PprSweepStats(ctypes.Structure):
+    _fields_ = [
+        ("device_ms", ctypes.c_double),
+        ("edges", ctypes.c_int64),
+        ("algo_bytes", ctypes.c_int64),
+        ("wave_sources", ctypes.c_int64),
+        ("wg_sources", ctypes.c_int64),
+        ("slice_sources", ctypes.c_int64),
+        ("chunks", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -205,6 +218,9 @@ def lib() -> ctypes.CDLL:
         "ppr_grank_plan_propagate": (ctypes.c_int, [vp, i32, i64, vp, i32, i32, u32, vp, i64, vp, i64, vp]),
         "ppr_grank_plan_propagate_t": (ctypes.c_int, [vp, i32, i64, vp, i32, i32, u32, vp, i64, vp, i64, vp]),
         "ppr_grank_plan_device": (ctypes.c_int, [vp, ctypes.POINTER(i32)]),
+        "ppr_grank_plan_sweep": (ctypes.c_int, [vp, i32, i64, vp, u32, u32, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "ppr_grank_plan_sweep_vectors": (ctypes.c_int, [vp, i64, i32, vp, vp, vp, u32, u32, i64, u32, vp, vp, vp, vp, vp, vp,
+                                                         vp, vp, vp]),
         "ppr_host_alloc": (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
         "ppr_host_free": (None, [vp]),
         "ppr_grank_plan_stream": (vp, [vp]),

@@ -365,6 +365,10 @@ struct ppr_plan {
   unsigned char* d_ps = nullptr;      // a pass's postings, both sort buffers, digit counts, run starts
   unsigned char* d_pt = nullptr;      // a pass's chunk and fold tasks, partial rows
   size_t p_bytes = 0, pk_bytes = 0, ps_bytes = 0, pt_bytes = 0;
+  // sweep cuts (sweep.hip): grow-only and kept across calls
+  unsigned char* d_sw = nullptr;      // a chunk's rows, orders, volumes, verdicts, tier lists, results
+  unsigned char* d_swh = nullptr;     // slice tasks and their 64-bit histogram rows
+  size_t sw_bytes = 0, swh_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -430,6 +434,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_q); hipFree(p->d_ql);
   hipFree(p->d_r); hipFree(p->d_rl); hipFree(p->d_rt);
   hipFree(p->d_p); hipFree(p->d_pk); hipFree(p->d_ps); hipFree(p->d_pt);
+  hipFree(p->d_sw); hipFree(p->d_swh);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (p->ev_rp) hipEventDestroy(p->ev_rp);

@@ -96,6 +96,28 @@ class RQueryResult:
                 for q, k in enumerate(self.lens)]
 
 
+@dataclass
+class SweepResult:
+    """Answer of GrankPlan.sweep / sweep_vectors: row i = the sweep of source (or vector) i and its
+    prefix of lowest conductance."""
+    order: np.ndarray      # int32 [S, width] the swept members in sweep order, -1 padded
+    swept: np.ndarray      # int32 [S] members swept (before max_size and the volume cap stopped it)
+    size: np.ndarray       # int32 [S] members of the best prefix, 0: none admissible
+    cut: np.ndarray        # int64 [S] edges leaving it
+    vol: np.ndarray        # int64 [S] its volume
+    phi: np.ndarray        # float64 [S] cut / min(vol, m - vol), +inf with size 0
+    profile_cut: Optional[np.ndarray] = None   # int64 [S, width] cut_j at j - 1, -1 padded (profile=True)
+    profile_vol: Optional[np.ndarray] = None   # int64 [S, width] vol_j at j - 1
+
+    def sets(self):
+        """the best set of each row: int32 arrays of dense ids, in sweep order"""
+        return [self.order[i, :int(k)].copy() for i, k in enumerate(self.size)]
+
+    def to_dicts(self, csr: Csr):
+        """one {graph key: rank in the sweep} per row, the best sets keyed by the graph's own keys"""
+        return [{csr.key(int(v)): j for j, v in enumerate(self.order[i, :int(k)])} for i, k in enumerate(self.size)]
+
+
 def normalize_queries(queries, weights=None):
     """The CSR form ppr_grank_plan_query takes: (qptr int64 [Q+1], seeds int32, weights float64 or
     None). `queries` is (qptr, seeds) arrays or a sequence of seed sequences; `weights` a flat array
@@ -135,6 +157,46 @@ def normalize_queries(queries, weights=None):
     if len(w) != len(seeds):
         raise ValueError(f"weights: {len(w)} entries for {len(seeds)} seeds")
     return qptr, seeds, w
+
+
+def normalize_vectors(ids_or_result, scores=None, lens=None):
+    """The rows ppr_grank_plan_sweep_vectors takes: (ids int32 [R, W], scores float64 [R, W], lens
+    int32 [R]). `ids_or_result` is a QueryResult (or any object with .ids / .scores / .lens) or an id
+    array, then with `scores`; `lens` None: a row ends at its first id -1. Shape mismatches raise
+    ValueError."""
+    if scores is None and all(hasattr(ids_or_result, f) for f in ("ids", "scores", "lens")):
+        if lens is not None:
+            raise ValueError("lens given with a result object that has its own")
+        ids_or_result, scores, lens = ids_or_result.ids, ids_or_result.scores, ids_or_result.lens
+    if scores is None:
+        raise ValueError("scores are required with an id array")
+    raw = np.asarray(ids_or_result)
+    if raw.ndim != 2:
+        raise ValueError(f"ids must be 2-D [rows, width], not {raw.ndim}-D")
+    if raw.size and (raw.min() < -2**31 or raw.max() >= 2**31):
+        raise ValueError("ids must fit in int32")
+    ids = np.ascontiguousarray(raw, dtype=np.int32)
+    sc = np.ascontiguousarray(scores, dtype=np.float64)
+    if sc.shape != ids.shape:
+        raise ValueError(f"scores have shape {sc.shape}, ids {ids.shape}")
+    if lens is None:
+        ln = np.where((ids < 0).any(axis=1), (ids < 0).argmax(axis=1), ids.shape[1]).astype(np.int32)
+    else:
+        ln = np.ascontiguousarray(np.asarray(lens).reshape(-1), dtype=np.int32)
+        if len(ln) != ids.shape[0]:
+            raise ValueError(f"lens: {len(ln)} entries for {ids.shape[0]} rows")
+    return ids, sc, ln
+
+
+def sweep_arguments(min_size, max_size, max_vol):
+    """(min_size, max_size, max_vol) as the C call takes them (None: 0, the library's default); a value
+    that its unsigned / signed words cannot carry is refused here, as PprError(invalid argument)"""
+    mn, mx, mv = int(min_size), 0 if max_size is None else int(max_size), 0 if max_vol is None else int(max_vol)
+    if not (0 <= mn < 2**32) or not (0 <= mx < 2**32) or not (-2**63 <= mv < 2**63):
+        raise _lib.PprError(1, "plan_sweep")
+    if max_size is not None and mx == 0:  # (0 means "the row width" only as the default)
+        raise _lib.PprError(1, "plan_sweep")
+    return mn, mx, mv
 
 
 def _stats_to(res: GrankResult, st: _lib.PprStats) -> None:
@@ -332,6 +394,61 @@ class GrankPlan:
                                                   iterations_run, _lib.PprRQueryStats(),
                                                   ("hits", "algo_bytes", "probe_queries", "scan_queries", "scans",
                                                    "chunks")))
+
+    # ---- sweep cuts (include/ppr_hip.h ppr_grank_plan_sweep / _sweep_vectors) ----
+    def _sweep(self, where, rows, row_width, call, min_size, max_size, max_vol, profile, stats):
+        mn, mx, mv = sweep_arguments(min_size, max_size, max_vol)
+        width = max(0, (min(mx, row_width) if where == "plan_sweep_vectors" else mx) if mx else row_width)
+        if mx > 4096:  # (no array of that width is allocated for a call the library refuses)
+            raise _lib.PprError(11, where)
+        order = np.full((rows, width), -1, dtype=np.int32)
+        swept = np.zeros(rows, dtype=np.int32)
+        size = np.zeros(rows, dtype=np.int32)
+        cut = np.zeros(rows, dtype=np.int64)
+        vol = np.zeros(rows, dtype=np.int64)
+        phi = np.full(rows, np.inf, dtype=np.float64)
+        pc = np.full((rows, width), -1, dtype=np.int64) if profile else None
+        pv = np.full((rows, width), -1, dtype=np.int64) if profile else None
+        st = _lib.PprSweepStats()
+        _lib.check(call(mn, mx, mv, 0, _lib.ptr(order), _lib.ptr(swept), _lib.ptr(size), _lib.ptr(cut), _lib.ptr(vol),
+                        _lib.ptr(phi), _lib.ptr(pc), _lib.ptr(pv), ctypes.byref(st)), where)
+        if stats is not None:
+            stats.update(device_ms=float(st.device_ms), edges=int(st.edges), algo_bytes=int(st.algo_bytes),
+                         wave_sources=int(st.wave_sources), wg_sources=int(st.wg_sources),
+                         slice_sources=int(st.slice_sources), chunks=int(st.chunks))
+        return SweepResult(order, swept, size, cut, vol, phi, pc, pv)
+
+    def sweep(self, sources=None, min_size: int = 1, max_size: Optional[int] = None, max_vol: Optional[int] = None,
+              profile: bool = False, iterations_run: Optional[int] = None, stats: Optional[dict] = None) -> SweepResult:
+        """The sweep cut of each source's resident PPR row, on the device (include/ppr_hip.h
+        ppr_grank_plan_sweep): the row ordered by score / out-degree, cut at `max_size` entries (None:
+        the row width L) and before the volume exceeds `max_vol` (None: half the graph's edges), and
+        the prefix of at least `min_size` members with the lowest conductance. sources: dense ids
+        (None: every node, in order); profile: also the cut and the volume of every prefix; stats: a
+        dict that receives the call's ppr_sweep_stats. The graph is taken as directed; pass a
+        symmetric graph for undirected clustering."""
+        S, src = self._prop_sources(sources)
+        it = self.iterations_run if iterations_run is None else iterations_run
+        fn = _lib.lib().ppr_grank_plan_sweep
+        if src is not None and S == 0:  # (an empty list is not "every node": the pointer must not be null)
+            src = np.zeros(1, dtype=np.int32)
+        return self._sweep("plan_sweep", S, self.L, lambda *tail: fn(self._p, it, S, _lib.ptr(src), *tail), min_size,
+                           max_size, max_vol, profile, stats)
+
+    def sweep_vectors(self, ids_or_result, scores=None, lens=None, min_size: int = 1, max_size: Optional[int] = None,
+                      max_vol: Optional[int] = None, profile: bool = False, stats: Optional[dict] = None) -> SweepResult:
+        """The same sweep over caller-supplied sparse vectors on the plan's graph (include/ppr_hip.h
+        ppr_grank_plan_sweep_vectors): a QueryResult (the community of a seed set), an exact PPR
+        top-K, or any (ids [R, W], scores [R, W], lens [R]) with W <= 4096 and distinct ids per row."""
+        ids, sc, ln = normalize_vectors(ids_or_result, scores, lens)
+        R, W = ids.shape
+        fn = _lib.lib().ppr_grank_plan_sweep_vectors
+        # a pointer for empty rows too: the C call refuses null pointers, and reads nothing through it
+        dummy = np.zeros(1, dtype=np.float64)
+        pi, ps = (_lib.ptr(ids), _lib.ptr(sc)) if ids.size else (_lib.ptr(dummy), _lib.ptr(dummy))
+        pl = _lib.ptr(ln) if len(ln) else _lib.ptr(dummy)
+        return self._sweep("plan_sweep_vectors", R, W, lambda *tail: fn(self._p, R, W, pi, ps, pl, *tail), min_size,
+                           max_size, max_vol, profile, stats)
 
     # ---- feature propagation (include/ppr_hip.h ppr_grank_plan_propagate / _propagate_t) ----
     @property

@@ -375,6 +375,65 @@ int ppr_grank_plan_propagate_t(ppr_plan* p, int32_t iterations_run, int64_t S, c
                                int64_t ldy, ppr_prop_stats* st);
 int ppr_grank_plan_device(ppr_plan* p, int32_t* device);
 
+/* ---- sweep-cut local clustering from the resident table ----
+ * The classic use of approximate PPR (no reference counterpart): local community detection by a
+ * sweep cut (Andersen, Chung & Lang, "Local graph partitioning using PageRank vectors"). A seed's
+ * PPR vector is swept in order of p[v] / deg(v); the prefix of lowest conductance is the seed's
+ * community. The plan holds every node's vector and the graph in HBM, so the sweep of every requested
+ * source is answered on the device, without downloading the slab.
+ * The graph is taken as the plan stores it: directed, out-edges only, repeated edges with their
+ * multiplicity (undirected clustering: pass a symmetric graph). deg(k) = row_ptr[k + 1] - row_ptr[k],
+ * m = row_ptr[n]. Per source u, with B[u] its current row after `iterations_run` iterations (the slot
+ * rule of ppr_grank_plan_fetch_slab; stored ids decoded to keys, undecodable ones skipped; the row
+ * length clamped to [0, L]) and its entries (k, s):
+ *   1. r = fl(s / (double)max(deg(k), 1)), one IEEE fp64 divide; the entries are sorted by (r
+ *      descending, k ascending) and the first max_size are kept (max_size = 0: the row width L).
+ *   2. Walking that order with vol += deg(k) in int64, the sweep stops BEFORE the first entry that
+ *      would make vol > max_vol (max_vol = 0: floor(m / 2)). The `swept` entries before the stop are
+ *      the sweep, with ranks 0 .. swept - 1; a source walks at most max_vol edges.
+ *   3. For j = 1 .. swept: vol_j = sum of deg over the first j members; internal_j = the edges a -> b
+ *      with both endpoints among the first j (self-loops count); cut_j = vol_j - internal_j;
+ *      den_j = min(vol_j, m - vol_j); all int64.
+ *   4. Among j in [min_size, swept] with den_j > 0 the smallest cut_j / den_j wins, compared exactly
+ *      (cut_a den_b < cut_b den_a with 128-bit products), ties to the smaller j: out_size = j, out_cut,
+ *      out_vol, out_phi = (double)cut / (double)den. With no admissible j (a dangling source's
+ *      one-entry row, swept < min_size): size 0, cut = vol = 0, phi = +inf.
+ * width = max_size ? max_size : L (vectors: max_size ? min(max_size, width_in) : width_in). Row i of
+ * out_order (S * width) holds the swept members in order, then -1; out_swept[i] their number; row i
+ * of prof_cut / prof_vol (S * width each, both or neither) holds cut_j / vol_j at j - 1, then -1.
+ * sources: S dense ids, repeats allowed; NULL: S must equal n and position i is source i.
+ * ppr_grank_plan_sweep_vectors sweeps R caller-supplied sparse vectors instead (a query's result
+ * rows: the community of a seed set; an exact PPR top-K): rows of width_in (<= 4096) ids / scores, the
+ * first lens[i] of row i meaningful, the same steps from 1 on.
+ * The result depends only on the slab (or the vectors), the graph and the arguments: not on the tier
+ * that answered a source, the slicing of its walk, the chunking, the knobs or the order of the sources.
+ * Host pointers; synchronous on the plan's stream; writes nothing into the slabs or the top-K output.
+ * Errors, all decided on the host before any kernel starts: PPR_ERR_ARG (null plan or pointers, S < 0,
+ * NULL sources with S != n, min_size = 0 or > width, max_vol < 0 or > m, only one of the two profile
+ * pointers, unknown flag bits -- none is defined --, an MC plan; vectors: a length outside
+ * [0, width_in], a negative / NaN / infinite score, a repeated id within a row), PPR_ERR_RANGE
+ * (max_size > 4096 or width_in > 4096), PPR_ERR_SOURCE (a source or id outside [0, n)).
+ * algo_bytes = the bytes the algorithm has to move: per row entry 28 (id 4, score 8, the two row
+ * pointer words of its degree 16); per walked edge 4; per source 4 * width + 36 (its order and the
+ * five result words), plus 16 * width with profiles. */
+typedef struct ppr_sweep_stats {
+  double device_ms;          /* HIP events around the kernels; uploads and downloads excluded */
+  int64_t edges;             /* edges walked = sum of vol_swept over the sources */
+  int64_t algo_bytes;        /* see above */
+  int64_t wave_sources, wg_sources, slice_sources;   /* sources answered by each tier */
+  int32_t chunks; int32_t reserved;
+} ppr_sweep_stats;
+int ppr_grank_plan_sweep(ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources,
+                         uint32_t min_size, uint32_t max_size, int64_t max_vol, uint32_t flags,
+                         int32_t* out_order, int32_t* out_swept, int32_t* out_size, int64_t* out_cut,
+                         int64_t* out_vol, double* out_phi, int64_t* prof_cut, int64_t* prof_vol,
+                         ppr_sweep_stats* st);
+int ppr_grank_plan_sweep_vectors(ppr_plan* p, int64_t R, int32_t width_in, const int32_t* ids,
+                                 const double* scores, const int32_t* lens, uint32_t min_size,
+                                 uint32_t max_size, int64_t max_vol, uint32_t flags, int32_t* out_order,
+                                 int32_t* out_swept, int32_t* out_size, int64_t* out_cut, int64_t* out_vol,
+                                 double* out_phi, int64_t* prof_cut, int64_t* prof_vol, ppr_sweep_stats* st);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
