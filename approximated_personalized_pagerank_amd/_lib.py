@@ -21,7 +21,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libppr_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 # every file the library is compiled from (csrc/ plus the public header), in digest order
-CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "sweep.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
+CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "sweep.hip", "subgraph.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
 # every header of csrc/ (a new one can not be left out of the provenance digest) and the C ABI
 CSRC_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "ppr_hip.h")]
 
@@ -60,6 +60,7 @@ PPR_RQUERY_EXCLUDE_TARGETS = 1  # ppr_grank_plan_rquery: drop the sources that a
 PPR_PROP_F32, PPR_PROP_BF16 = 0, 1  # ppr_grank_plan_propagate(_t): feature dtype
 PPR_PROP_ROW_NORMALIZE = 1  # ... weights s_j / W, W the row's scores summed in stored order
 PPR_PROP_CHUNK = 512  # postings per chunk of the transposed sum (part of the contract)
+PPR_SUBG_ROOT_FIRST, PPR_SUBG_IDX64 = 1, 2  # ppr_grank_plan_subgraphs: the source is member 0; int64 indices
 
 ERRORS = {
     0: "ok",
@@ -173,6 +174,22 @@ class PprSweepStats(ctypes.Structure):
     ]
 
 
+class PprSubgStats(ctypes.Structure):
+    _fields_ = [
+        ("device_ms", ctypes.c_double),
+        ("edges_walked", ctypes.c_int64),
+        ("edges", ctypes.c_int64),
+        ("nodes", ctypes.c_int64),
+        ("capped_members", ctypes.c_int64),
+        ("algo_bytes", ctypes.c_int64),
+        ("wave_sources", ctypes.c_int64),
+        ("wg_sources", ctypes.c_int64),
+        ("slice_sources", ctypes.c_int64),
+        ("chunks", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -221,6 +238,8 @@ def lib() -> ctypes.CDLL:
         "ppr_grank_plan_sweep": (ctypes.c_int, [vp, i32, i64, vp, u32, u32, i64, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ppr_grank_plan_sweep_vectors": (ctypes.c_int, [vp, i64, i32, vp, vp, vp, u32, u32, i64, u32, vp, vp, vp, vp, vp, vp,
                                                          vp, vp, vp]),
+        "ppr_grank_plan_subgraphs": (ctypes.c_int, [vp, i32, i64, vp, u32, i64, u32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
+                                                     vp]),
         "ppr_host_alloc": (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
         "ppr_host_free": (None, [vp]),
         "ppr_grank_plan_stream": (vp, [vp]),

@@ -369,6 +369,10 @@ struct ppr_plan {
   unsigned char* d_sw = nullptr;      // a chunk's rows, orders, volumes, verdicts, tier lists, results
   unsigned char* d_swh = nullptr;     // slice tasks and their 64-bit histogram rows
   size_t sw_bytes = 0, swh_bytes = 0;
+  // induced subgraph batches (subgraph.hip): grow-only and kept across calls
+  unsigned char* d_sg = nullptr;      // a chunk's sources, members, score bits, verdicts, offsets, tier lists
+  unsigned char* d_sgh = nullptr;     // a walk batch's per-member and per-group counts, their scans, slice tasks
+  size_t sg_bytes = 0, sgh_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -435,6 +439,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_r); hipFree(p->d_rl); hipFree(p->d_rt);
   hipFree(p->d_p); hipFree(p->d_pk); hipFree(p->d_ps); hipFree(p->d_pt);
   hipFree(p->d_sw); hipFree(p->d_swh);
+  hipFree(p->d_sg); hipFree(p->d_sgh);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (p->ev_rp) hipEventDestroy(p->ev_rp);

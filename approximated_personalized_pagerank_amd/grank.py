@@ -118,6 +118,69 @@ class SweepResult:
         return [{csr.key(int(v)): j for j, v in enumerate(self.order[i, :int(k)])} for i, k in enumerate(self.size)]
 
 
+@dataclass
+class SubgraphBatch:
+    """Answer of GrankPlan.subgraphs: the subgraphs induced by each source's top PPR neighbours, as one
+    batched graph. Tensors live on the plan's device; member j of position i has the batch id
+    node_ptr[i] + j, and the edges of position i are edge_ptr[i] .. edge_ptr[i + 1] - 1."""
+    nodes: "torch.Tensor"            # [N] dense ids of the members, position by position, in rank order
+    scores: "Optional[torch.Tensor]"  # [N] float64, the row's score of each member (scores=True)
+    rowptr: "torch.Tensor"           # [N + 1] CSR over batch ids
+    col: "torch.Tensor"              # [E] batch id of every edge's target
+    row: "Optional[torch.Tensor]"    # [E] batch id of every edge's source (coo=True)
+    eid: "Optional[torch.Tensor]"    # [E] int64, the edge's position in the plan's edge array (edge_ids=True)
+    node_ptr: np.ndarray             # int64 [S + 1]
+    edge_ptr: np.ndarray             # int64 [S + 1]
+
+    @property
+    def num_graphs(self) -> int:
+        return len(self.node_ptr) - 1
+
+    @property
+    def num_nodes(self) -> int:
+        return int(self.node_ptr[-1])
+
+    @property
+    def num_edges(self) -> int:
+        return int(self.edge_ptr[-1])
+
+    @property
+    def edge_index(self):
+        """[2, E]: row over col, the COO form message-passing layers take (needs coo=True)"""
+        import torch
+        if self.row is None:
+            raise ValueError("edge_index needs the COO rows: call subgraphs(coo=True)")
+        return torch.stack((self.row, self.col))
+
+    @property
+    def roots(self):
+        """[S] int64, the batch id of member 0 of every position (the source itself with root_first=True)"""
+        import torch
+        return torch.as_tensor(self.node_ptr[:-1].copy(), dtype=torch.int64, device=self.nodes.device)
+
+    @property
+    def batch(self):
+        """[N] int64, the position every node belongs to"""
+        import torch
+        counts = torch.as_tensor(np.diff(self.node_ptr), dtype=torch.int64, device=self.nodes.device)
+        return torch.repeat_interleave(torch.arange(self.num_graphs, dtype=torch.int64, device=self.nodes.device), counts)
+
+
+def subgraph_arguments(size, max_deg, edge_capacity=None):
+    """(size, max_deg, edge_capacity) as the C call takes them (None: 0, the library's default; no
+    capacity: None); a value its words cannot carry is refused here, as PprError(invalid argument),
+    a size the library would refuse as PprError(out of range)"""
+    sz, md = 0 if size is None else int(size), 0 if max_deg is None else int(max_deg)
+    cap = None if edge_capacity is None else int(edge_capacity)
+    if not (0 <= sz < 2**32) or not (0 <= md < 2**63) or (cap is not None and not (0 <= cap < 2**63)):
+        raise _lib.PprError(1, "plan_subgraphs")
+    if (size is not None and sz == 0) or (max_deg is not None and md == 0):  # (0 means "none" only as the default)
+        raise _lib.PprError(1, "plan_subgraphs")
+    if sz > 4096:  # (no tensor is allocated for a call the library refuses)
+        raise _lib.PprError(11, "plan_subgraphs")
+    return sz, md, cap
+
+
 def normalize_queries(queries, weights=None):
     """The CSR form ppr_grank_plan_query takes: (qptr int64 [Q+1], seeds int32, weights float64 or
     None). `queries` is (qptr, seeds) arrays or a sequence of seed sequences; `weights` a flat array
@@ -449,6 +512,74 @@ class GrankPlan:
         pl = _lib.ptr(ln) if len(ln) else _lib.ptr(dummy)
         return self._sweep("plan_sweep_vectors", R, W, lambda *tail: fn(self._p, R, W, pi, ps, pl, *tail), min_size,
                            max_size, max_vol, profile, stats)
+
+    # ---- induced subgraph batches (include/ppr_hip.h ppr_grank_plan_subgraphs) ----
+    def subgraphs(self, sources=None, size: Optional[int] = None, max_deg: Optional[int] = None, root_first: bool = False,
+                  index_dtype=None, coo: bool = True, edge_ids: bool = False, scores: bool = True,
+                  iterations_run: Optional[int] = None, edge_capacity: Optional[int] = None,
+                  stats: Optional[dict] = None) -> SubgraphBatch:
+        """The subgraph each source's top PPR neighbours induce, for a whole minibatch, on the device
+        (include/ppr_hip.h ppr_grank_plan_subgraphs): the `size` best entries of the source's resident
+        row (None: the row width L) by (score desc, id asc), the source first with `root_first`, and
+        every stored edge between them (members of more than `max_deg` out-edges emit none). Returns
+        a SubgraphBatch of torch tensors on the plan's device: `index_dtype` torch.int64 (default) or
+        torch.int32; coo: also the COO rows; edge_ids: also every edge's position in the graph's edge
+        array; scores: also the members' scores. By default a count-only call sizes the tensors exactly;
+        `edge_capacity` skips it (a guess that is too small costs one more call). sources: dense ids
+        (None: every node, in order); stats: a dict that receives the call's ppr_subg_stats."""
+        import torch
+        if index_dtype is None:
+            index_dtype = torch.int64
+        if index_dtype not in (torch.int32, torch.int64):
+            raise TypeError(f"index_dtype must be torch.int32 or torch.int64, not {index_dtype}")
+        sz, md, cap = subgraph_arguments(size, max_deg, edge_capacity)
+        S, src = self._prop_sources(sources)
+        if src is not None and S == 0:  # (an empty list is not "every node": the pointer must not be null)
+            src = np.zeros(1, dtype=np.int32)
+        it = self.iterations_run if iterations_run is None else iterations_run
+        flags = (_lib.PPR_SUBG_ROOT_FIRST if root_first else 0) | (_lib.PPR_SUBG_IDX64 if index_dtype == torch.int64 else 0)
+        node_ptr = np.zeros(S + 1, dtype=np.int64)
+        edge_ptr = np.zeros(S + 1, dtype=np.int64)
+        st = _lib.PprSubgStats()
+        fn = _lib.lib().ppr_grank_plan_subgraphs
+        dev = torch.device("cuda", self.device)
+
+        def call(ncap, ecap, t):
+            return fn(self._p, it, S, _lib.ptr(src), sz, md, flags, ncap, ecap, _lib.ptr(node_ptr), _lib.ptr(edge_ptr),
+                      *(None if x is None else x.data_ptr() for x in t), ctypes.byref(st))
+
+        def alloc(ncap, ecap):
+            # (one spare element each: data_ptr() of an empty tensor is null, and a null pointer means count-only)
+            t = (torch.empty(ncap + 1, dtype=index_dtype, device=dev),
+                 torch.empty(ncap + 1, dtype=torch.float64, device=dev) if scores else None,
+                 torch.empty(ncap + 1, dtype=index_dtype, device=dev),
+                 torch.empty(ecap + 1, dtype=index_dtype, device=dev),
+                 torch.empty(ecap + 1, dtype=index_dtype, device=dev) if coo else None,
+                 torch.empty(ecap + 1, dtype=torch.int64, device=dev) if edge_ids else None)
+            torch.cuda.current_stream(dev).synchronize()  # the tensors are the plan's stream's from here on
+            return t
+
+        if cap is None:
+            _lib.check(call(0, 0, (None,) * 6), "plan_subgraphs")
+            ncap, ecap = int(node_ptr[-1]), int(edge_ptr[-1])
+        else:
+            ncap, ecap = S * min(sz or self.L, self.L), cap
+        t = alloc(ncap, ecap)
+        rc = call(ncap, ecap, t)
+        if rc == 11 and cap is not None and (int(node_ptr[-1]) > ncap or int(edge_ptr[-1]) > ecap):
+            ncap, ecap = int(node_ptr[-1]), int(edge_ptr[-1])  # (the refused call completed both host arrays)
+            t = alloc(ncap, ecap)
+            rc = call(ncap, ecap, t)
+        _lib.check(rc, "plan_subgraphs")
+        N, E = int(node_ptr[-1]), int(edge_ptr[-1])
+        if stats is not None:
+            stats.update(device_ms=float(st.device_ms), edges_walked=int(st.edges_walked), edges=int(st.edges),
+                         nodes=int(st.nodes), capped_members=int(st.capped_members), algo_bytes=int(st.algo_bytes),
+                         wave_sources=int(st.wave_sources), wg_sources=int(st.wg_sources),
+                         slice_sources=int(st.slice_sources), chunks=int(st.chunks))
+        nodes_t, sc_t, rowptr_t, col_t, row_t, eid_t = t
+        return SubgraphBatch(nodes_t[:N], None if sc_t is None else sc_t[:N], rowptr_t[:N + 1], col_t[:E],
+                             None if row_t is None else row_t[:E], None if eid_t is None else eid_t[:E], node_ptr, edge_ptr)
 
     # ---- feature propagation (include/ppr_hip.h ppr_grank_plan_propagate / _propagate_t) ----
     @property

@@ -434,6 +434,84 @@ int ppr_grank_plan_sweep_vectors(ppr_plan* p, int64_t R, int32_t width_in, const
                                  int32_t* out_swept, int32_t* out_size, int64_t* out_cut, int64_t* out_vol,
                                  double* out_phi, int64_t* prof_cut, int64_t* prof_vol, ppr_sweep_stats* st);
 
+/* ---- PPR-induced subgraph batches from the resident table ----
+ * Subgraph sampling by PPR for GNN minibatches (no reference counterpart): for each root of a batch
+ * its top PPR neighbours and the subgraph they induce (ShaDow-GNN, Zeng et al., "Decoupling the Depth
+ * and Scope of Graph Neural Networks"; GraphSAINT's and PPRGo's PPR samplers), as one batched CSR /
+ * COO in DEVICE memory, without downloading the slab.
+ * The graph is taken as the plan stores it: directed, out-edges only, repeated edges with their
+ * multiplicity, self-loops kept, bit 31 of a stored target masked off; deg(k) = row_ptr[k + 1] -
+ * row_ptr[k]. GRank plans only. sources: S dense ids (host), repeats allowed; NULL: S must equal n
+ * and position i is source i.
+ * Members. For position i with u = sources[i]:
+ *   1. B[u] is the current row of u after `iterations_run` iterations (the slot rule of
+ *      ppr_grank_plan_fetch_slab; stored ids decoded to keys, undecodable ones skipped; the row
+ *      length clamped to [0, L]).
+ *   2. Its entries are ordered by (score descending, key ascending); scores are >= +0, so their bit
+ *      patterns order like the values.
+ *   3. With PPR_SUBG_ROOT_FIRST the entry whose key is u moves to the front, the others keep their
+ *      order (a GRank row always holds it; were it absent, the flag has no effect for that position).
+ *   4. The first `size` entries are kept (size = 0: the row width L): the c_i = min(size, decodable
+ *      length) members of position i, with ranks 0 .. c_i - 1.
+ * Edges. A member a with max_deg > 0 and deg(a) > max_deg emits no out-edges (it stays a node and
+ * still receives edges; max_deg = 0: no cap). Every other member a emits one edge per position p of
+ * its adjacency list whose target col[p] & 0x7fffffff is a member of the same position. The edges of
+ * the batch are ordered by (position i, rank of a, p) ascending: the graph's own order, filtered.
+ * Outputs, with N = sum c_i and E = all edges; node_ptr / edge_ptr are HOST arrays, the others
+ * DEVICE pointers:
+ *   node_ptr[S + 1], edge_ptr[S + 1]  int64, exclusive prefix sums of c_i / of the edges per position
+ *   nodes[N]       global keys: member j of position i at node_ptr[i] + j, which is its batch id
+ *   scores[N]      fp64, optional (NULL: not written): the row's score of each member, bit for bit
+ *   rowptr[N + 1]  rowptr[node_ptr[i] + j] = edge_ptr[i] + edges emitted by the members of position i
+ *                  before j; rowptr[N] = E
+ *   col[E]         batch id of the target
+ *   row[E]         optional: batch id of the emitting member (COO)
+ *   eid[E]         int64, optional: the position p in the plan's edge array
+ * nodes, rowptr, col and row share one index type: int32, or int64 with PPR_SUBG_IDX64.
+ * The result depends only on the slab, the graph and the arguments: not on the tier that answered a
+ * source, the slicing of its walk, the chunking, the knobs or the order of the sources (a position's
+ * rows are the same up to its node_ptr / edge_ptr offsets wherever it stands). No float atomics; no
+ * output position is decided by the arrival order of atomics (the edges are counted per 64-edge
+ * group of a fixed numbering of the walk, the counts are scanned, and the second pass writes every
+ * hit at its group's offset plus its lane's rank among the group's hits). Synchronous on the plan's
+ * stream (the caller synchronises the stream that produced the output tensors first); writes nothing
+ * into the slabs or the plan's top-K output.
+ * Capacities. node_cap / edge_cap are the element capacities of the device arrays: nodes and scores
+ * hold node_cap elements, rowptr node_cap + 1, col / row / eid edge_cap. A COUNT-ONLY call has every
+ * device pointer NULL and both capacities 0: node_ptr / edge_ptr are filled, PPR_OK. When N > node_cap
+ * or E > edge_cap the call returns PPR_ERR_RANGE with node_ptr / edge_ptr complete and valid (the
+ * caller allocates from them); the contents of the device arrays are then unspecified, and nothing is
+ * written at or beyond index node_cap of nodes / scores / rowptr or edge_cap of col / row / eid.
+ * N or E above 2^31 - 1 without PPR_SUBG_IDX64: PPR_ERR_RANGE as well, host arrays complete.
+ * A source whose uncapped members have more than 2^30 out-edges in total: PPR_ERR_RANGE (set max_deg).
+ * Refusals, all decided on the host before any kernel starts, in this order; they leave every output
+ * untouched (st is cleared): PPR_ERR_ARG (null plan, an MC plan, iterations_run < 0, null node_ptr or
+ * edge_ptr, S < 0; then NULL sources with S != n; then unknown flag bits; then max_deg < 0 or a
+ * negative capacity; then some but not all of nodes / rowptr / col NULL; then all three NULL with an
+ * optional pointer or a capacity given), PPR_ERR_RANGE (size > 4096 or S > 2^30), PPR_ERR_SOURCE (a
+ * source outside [0, n)).
+ * Stats: edges_walked = sum of deg over the uncapped members; capped_members = members that max_deg
+ * silenced; algo_bytes = the bytes the algorithm has to move, with X the index size (4 or 8): per
+ * decodable row entry 12 (id and score); per member 16 (the two row pointer words of its degree)
+ * and, unless count-only, 2 X (nodes, rowptr) + 8 with scores; per walked edge 4 in the count pass
+ * and 4 more when the emit pass ran; per 64-edge group 8 (its count written, its offset read); per
+ * emitted edge X, + X with row, + 8 with eid. */
+enum { PPR_SUBG_ROOT_FIRST = 1, PPR_SUBG_IDX64 = 2 };
+typedef struct ppr_subg_stats {
+  double device_ms;          /* HIP events around the kernels; uploads and downloads excluded */
+  int64_t edges_walked;
+  int64_t edges, nodes;      /* E, N */
+  int64_t capped_members;
+  int64_t algo_bytes;        /* see above */
+  int64_t wave_sources, wg_sources, slice_sources;   /* sources answered by each tier */
+  int32_t chunks; int32_t reserved;
+} ppr_subg_stats;
+int ppr_grank_plan_subgraphs(ppr_plan* p, int32_t iterations_run, int64_t S, const int32_t* sources,
+                             uint32_t size, int64_t max_deg, uint32_t flags, int64_t node_cap,
+                             int64_t edge_cap, int64_t* node_ptr, int64_t* edge_ptr, void* nodes,
+                             double* scores, void* rowptr, void* col, void* row, int64_t* eid,
+                             ppr_subg_stats* st);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
