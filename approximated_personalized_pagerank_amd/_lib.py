@@ -21,7 +21,7 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG_DIR, "libppr_hip.so")
 CSRC = os.path.join(PKG_DIR, "csrc")
 # every file the library is compiled from (csrc/ plus the public header), in digest order
-CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "sweep.hip", "subgraph.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
+CSRC_SOURCES = ["grank.hip", "mccp2.hip", "query.hip", "rquery.hip", "propagate.hip", "sweep.hip", "subgraph.hip", "pairs.hip", "exact_ppr.hip", "partition.hip", "host_graph.cpp"]
 # every header of csrc/ (a new one can not be left out of the provenance digest) and the C ABI
 CSRC_HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "ppr_hip.h")]
 
@@ -190,6 +190,23 @@ class PprSubgStats(ctypes.Structure):
     ]
 
 
+class PprPairsStats(ctypes.Structure):
+    _fields_ = [
+        ("device_ms", ctypes.c_double),
+        ("pairs", ctypes.c_int64),
+        ("groups", ctypes.c_int64),
+        ("lookup_pairs", ctypes.c_int64),
+        ("overlap_pairs", ctypes.c_int64),
+        ("entries_read", ctypes.c_int64),
+        ("algo_bytes", ctypes.c_int64),
+        ("wave_groups", ctypes.c_int64),
+        ("wg_groups", ctypes.c_int64),
+        ("split_groups", ctypes.c_int64),
+        ("chunks", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+    ]
+
+
 _lib = None
 
 
@@ -240,6 +257,7 @@ def lib() -> ctypes.CDLL:
                                                          vp, vp, vp]),
         "ppr_grank_plan_subgraphs": (ctypes.c_int, [vp, i32, i64, vp, u32, i64, u32, i64, i64, vp, vp, vp, vp, vp, vp, vp, vp,
                                                      vp]),
+        "ppr_grank_plan_pairs": (ctypes.c_int, [vp, i32, i64, vp, vp, vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
         "ppr_host_alloc": (ctypes.c_int, [i64, ctypes.POINTER(vp)]),
         "ppr_host_free": (None, [vp]),
         "ppr_grank_plan_stream": (vp, [vp]),

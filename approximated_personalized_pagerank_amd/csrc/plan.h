@@ -373,6 +373,9 @@ struct ppr_plan {
   unsigned char* d_sg = nullptr;      // a chunk's sources, members, score bits, verdicts, offsets, tier lists
   unsigned char* d_sgh = nullptr;     // a walk batch's per-member and per-group counts, their scans, slice tasks
   size_t sg_bytes = 0, sgh_bytes = 0;
+  // node-pair scores (pairs.hip): grow-only and kept across calls
+  unsigned char* d_pr = nullptr;      // a chunk's sources, candidates, tasks, rank rows, counters and outputs
+  size_t pr_bytes = 0;
   // MCCompletePathV2 (mccp2.hip)
   bool mc = false;
   int32_t* d_mc_walk = nullptr;       // walk set W (nodes read before their final basket exists)
@@ -440,6 +443,7 @@ inline void plan_free(ppr_plan* p) {
   hipFree(p->d_p); hipFree(p->d_pk); hipFree(p->d_ps); hipFree(p->d_pt);
   hipFree(p->d_sw); hipFree(p->d_swh);
   hipFree(p->d_sg); hipFree(p->d_sgh);
+  hipFree(p->d_pr);
   if (p->h_sv_pin) hipHostFree(p->h_sv_pin);
   if (p->ev_sv) hipEventDestroy(p->ev_sv);
   if (p->ev_rp) hipEventDestroy(p->ev_rp);

@@ -166,6 +166,129 @@ class SubgraphBatch:
         return torch.repeat_interleave(torch.arange(self.num_graphs, dtype=torch.int64, device=self.nodes.device), counts)
 
 
+PAIR_OUTPUTS = ("fwd", "bwd", "rank", "common", "dot")
+
+
+@dataclass
+class PairResult:
+    """Answer of GrankPlan.pairs / pair_scores: one entry per (source, candidate) pair, in candidate
+    order; group q = pairs gptr[q] .. gptr[q + 1] - 1, all scored against sources[q]. The arrays of
+    outputs that were not asked for are None."""
+    sources: np.ndarray              # int32 [Q]
+    candidates: np.ndarray           # int32 [P]
+    gptr: np.ndarray                 # int64 [Q + 1]
+    hit: np.ndarray                  # uint8 [P] bit 0: v is a key of B[u]; bit 1: u is a key of B[v]
+    src_len: np.ndarray              # int32 [Q] entries of B[u]
+    cand_len: np.ndarray             # int32 [P] entries of B[v]
+    fwd: Optional[np.ndarray] = None     # float64 [P] B[u][v], 0 when absent
+    bwd: Optional[np.ndarray] = None     # float64 [P] B[v][u], 0 when absent
+    rank: Optional[np.ndarray] = None    # int32 [P] position of v in B[u] by (score desc, id asc), -1 when absent
+    common: Optional[np.ndarray] = None  # int32 [P] keys the two rows share
+    dot: Optional[np.ndarray] = None     # float64 [P] exact dot product of the two rows, rounded once
+
+    @property
+    def pair_sources(self) -> np.ndarray:
+        """int32 [P]: the source of every pair"""
+        return np.repeat(self.sources, np.diff(self.gptr))
+
+    @property
+    def pair_src_len(self) -> np.ndarray:
+        """int32 [P]: len(B[u]) of every pair"""
+        return np.repeat(self.src_len, np.diff(self.gptr))
+
+    def jaccard(self) -> np.ndarray:
+        """common / (len_u + len_v - common) per pair, 0 where the denominator is 0 (needs "common")"""
+        if self.common is None:
+            raise ValueError('jaccard needs the overlap: ask for what=("common", ...)')
+        c = self.common.astype(np.float64)
+        den = self.pair_src_len.astype(np.float64) + self.cand_len.astype(np.float64) - c
+        return np.divide(c, den, out=np.zeros(len(c), dtype=np.float64), where=den > 0)
+
+    def cosine(self, norm2_u, norm2_v) -> np.ndarray:
+        """dot / sqrt(norm2_u * norm2_v) per pair, 0 where a norm is 0 (needs "dot"). norm2_u: the squared
+        norm of every group's source row (length Q) or of every pair's (length P); norm2_v: of every
+        pair's candidate row. The squared norm of row x is dot(x, x): plan.pair_scores(x, x, what=("dot",)).dot"""
+        if self.dot is None:
+            raise ValueError('cosine needs the dot products: ask for what=("dot", ...)')
+        nu = np.asarray(norm2_u, dtype=np.float64).reshape(-1)
+        nv = np.asarray(norm2_v, dtype=np.float64).reshape(-1)
+        P = len(self.candidates)
+        if len(nu) == len(self.sources) and len(nu) != P:
+            nu = np.repeat(nu, np.diff(self.gptr))
+        if len(nu) != P or len(nv) != P:
+            raise ValueError(f"norms: {len(nu)} and {len(nv)} values for {len(self.sources)} groups and {P} pairs")
+        den = np.sqrt(nu * nv)
+        return np.divide(self.dot, den, out=np.zeros(P, dtype=np.float64), where=den > 0)
+
+    def to_dicts(self, csr: Csr):
+        """one {graph key of the candidate: {output: value}} per group, keyed by the graph's own keys (a
+        candidate repeated within a group keeps its last entry)"""
+        names = [f for f in ("fwd", "bwd", "rank", "common", "dot") if getattr(self, f) is not None]
+        out = []
+        for q in range(len(self.sources)):
+            d = {}
+            for j in range(int(self.gptr[q]), int(self.gptr[q + 1])):
+                e = {f: getattr(self, f)[j].item() for f in names}
+                e["hit"] = int(self.hit[j])
+                d[csr.key(int(self.candidates[j]))] = e
+            out.append(d)
+        return out
+
+
+def _int32_ids(x, what):
+    flat = np.asarray(x, dtype=np.int64).reshape(-1)
+    if len(flat) and (flat.min() < -2**31 or flat.max() >= 2**31):
+        raise ValueError(f"{what} ids must fit in int32")
+    return np.ascontiguousarray(flat, dtype=np.int32)
+
+
+def normalize_groups(sources, candidates):
+    """The CSR form ppr_grank_plan_pairs takes: (gptr int64 [Q+1], sources int32 [Q], cands int32 [P]).
+    `candidates` is (gptr, cands) arrays or a sequence of candidate sequences, one per source. Shape
+    mismatches raise ValueError."""
+    src = _int32_ids(sources, "source")
+    gptr, cands, _ = normalize_queries(candidates)
+    if len(gptr) - 1 != len(src):
+        raise ValueError(f"candidates: {len(gptr) - 1} groups for {len(src)} sources")
+    return gptr, src, cands
+
+
+def normalize_pairs(u, v):
+    """Flat pairs (u[i], v[i]) grouped by source for ppr_grank_plan_pairs: returns (gptr, sources,
+    cands, order, inverse). The pairs are sorted by u with a stable sort (`order`: pair order[j] of the
+    caller stands at position j, so equal sources keep the caller's order of candidates); sources are the
+    distinct values of u ascending; `inverse` scatters back: result_in_caller_order = result[inverse].
+    Arrays of different lengths or more than one dimension raise ValueError."""
+    ua, va = np.asarray(u), np.asarray(v)
+    if ua.ndim != 1 or va.ndim != 1:
+        raise ValueError(f"u and v must be flat arrays, not {ua.ndim}-D and {va.ndim}-D")
+    if len(ua) != len(va):
+        raise ValueError(f"u has {len(ua)} entries, v {len(va)}")
+    ua, va = _int32_ids(ua, "source"), _int32_ids(va, "candidate")
+    order = np.argsort(ua, kind="stable")
+    su = ua[order]
+    if len(su):
+        first = np.flatnonzero(np.concatenate(([True], su[1:] != su[:-1])))
+        sources = su[first]
+        gptr = np.concatenate((first, [len(su)])).astype(np.int64)
+    else:
+        sources, gptr = np.zeros(0, dtype=np.int32), np.zeros(1, dtype=np.int64)
+    inverse = np.empty(len(order), dtype=np.int64)
+    inverse[order] = np.arange(len(order), dtype=np.int64)
+    return gptr, np.ascontiguousarray(sources), np.ascontiguousarray(va[order]), order, inverse
+
+
+def pair_outputs(what):
+    """the outputs named in `what`, validated: a tuple in PAIR_OUTPUTS order"""
+    if isinstance(what, str):
+        what = (what,)
+    what = tuple(what)
+    bad = [w for w in what if w not in PAIR_OUTPUTS]
+    if bad or not what:
+        raise ValueError(f"what must name some of {PAIR_OUTPUTS}, not {what!r}")
+    return tuple(w for w in PAIR_OUTPUTS if w in what)
+
+
 def subgraph_arguments(size, max_deg, edge_capacity=None):
     """(size, max_deg, edge_capacity) as the C call takes them (None: 0, the library's default; no
     capacity: None); a value its words cannot carry is refused here, as PprError(invalid argument),
@@ -580,6 +703,58 @@ class GrankPlan:
         nodes_t, sc_t, rowptr_t, col_t, row_t, eid_t = t
         return SubgraphBatch(nodes_t[:N], None if sc_t is None else sc_t[:N], rowptr_t[:N + 1], col_t[:E],
                              None if row_t is None else row_t[:E], None if eid_t is None else eid_t[:E], node_ptr, edge_ptr)
+
+    # ---- node-pair scores (include/ppr_hip.h ppr_grank_plan_pairs) ----
+    def _pairs(self, gptr, src, cands, what, iterations_run, stats) -> PairResult:
+        names = pair_outputs(what)
+        Q, P = len(src), len(cands)
+        it = self.iterations_run if iterations_run is None else iterations_run
+        out = {"fwd": np.zeros(P, dtype=np.float64) if "fwd" in names else None,
+               "bwd": np.zeros(P, dtype=np.float64) if "bwd" in names else None,
+               "rank": np.full(P, -1, dtype=np.int32) if "rank" in names else None,
+               "common": np.zeros(P, dtype=np.int32) if "common" in names else None,
+               "dot": np.zeros(P, dtype=np.float64) if "dot" in names else None}
+        hit = np.zeros(P, dtype=np.uint8)
+        slen = np.zeros(Q, dtype=np.int32)
+        clen = np.zeros(P, dtype=np.int32)
+        st = _lib.PprPairsStats()
+        # a pointer for empty arrays too: the C call refuses null pointers, and reads nothing through them
+        dummy = np.zeros(1, dtype=np.int64)
+        p = lambda a: None if a is None else (_lib.ptr(a) if a.size else _lib.ptr(dummy))
+        _lib.check(_lib.lib().ppr_grank_plan_pairs(self._p, it, Q, _lib.ptr(gptr), p(src), p(cands), 0, p(out["fwd"]),
+                                                   p(out["bwd"]), p(hit), p(out["rank"]), p(out["common"]), p(out["dot"]),
+                                                   p(slen), p(clen), ctypes.byref(st)), "plan_pairs")
+        if stats is not None:
+            stats.update(device_ms=float(st.device_ms), **{f: int(getattr(st, f)) for f in (
+                "pairs", "groups", "lookup_pairs", "overlap_pairs", "entries_read", "algo_bytes", "wave_groups", "wg_groups",
+                "split_groups", "chunks")})
+        return PairResult(src, cands, gptr, hit, slen, clen, **out)
+
+    def pairs(self, sources, candidates, what=PAIR_OUTPUTS, iterations_run: Optional[int] = None,
+              stats: Optional[dict] = None) -> PairResult:
+        """Scores of node pairs from the plan's resident baskets, on the device (include/ppr_hip.h
+        ppr_grank_plan_pairs): source sources[q] against each of its candidates. `candidates`: a sequence of
+        candidate sequences, one per source, or a (gptr, cands) CSR; `what`: some of "fwd" (B[u][v]), "bwd"
+        (B[v][u]), "rank" (the position of v in B[u] by score, for Hits@K and MRR), "common" (keys the rows
+        share) and "dot" (their exact dot product); the hit bits and both row lengths come with any of
+        them. Without "common" and "dot" only one 1/64 segment of a row is read per lookup. stats: a dict
+        that receives the call's ppr_pairs_stats."""
+        gptr, src, cands = normalize_groups(sources, candidates)
+        return self._pairs(gptr, src, cands, what, iterations_run, stats)
+
+    def pair_scores(self, u, v, what=PAIR_OUTPUTS, iterations_run: Optional[int] = None,
+                    stats: Optional[dict] = None) -> PairResult:
+        """pairs() for flat arrays: pair i is (u[i], v[i]). The pairs are grouped by source (a stable
+        sort, normalize_pairs) and the results scattered back: every per-pair array of the result is in
+        the caller's order, `sources` is u, `candidates` v, and every pair is a group of its own
+        (gptr = 0, 1, 2, ...)."""
+        gptr, src, cands, order, inverse = normalize_pairs(u, v)
+        r = self._pairs(gptr, src, cands, what, iterations_run, stats)
+        back = lambda a: None if a is None else np.ascontiguousarray(a[inverse])
+        n = len(inverse)
+        return PairResult(np.ascontiguousarray(r.pair_sources[inverse]), back(r.candidates), np.arange(n + 1, dtype=np.int64),
+                          back(r.hit), np.ascontiguousarray(r.pair_src_len[inverse]), back(r.cand_len), back(r.fwd),
+                          back(r.bwd), back(r.rank), back(r.common), back(r.dot))
 
     # ---- feature propagation (include/ppr_hip.h ppr_grank_plan_propagate / _propagate_t) ----
     @property

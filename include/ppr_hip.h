@@ -512,6 +512,76 @@ int ppr_grank_plan_subgraphs(ppr_plan* p, int32_t iterations_run, int64_t S, con
                              double* scores, void* rowptr, void* col, void* row, int64_t* eid,
                              ppr_subg_stats* st);
 
+/* ---- node-pair scores from the resident table ----
+ * The most basic question about the table (no reference counterpart): what is B[u][v], and how
+ * similar are the rows of u and v? The PPR score of a pair is the standard link-prediction feature
+ * and Hits@K / MRR need the rank of a target inside the source's row; candidate re-ranking needs the
+ * forward score, the backward score and the row overlap; node similarity the Jaccard or cosine of two
+ * rows. Answered on the device, without downloading the slab. GRank plans only.
+ * Q groups as a CSR: gptr[Q + 1] (gptr[0] = 0), sources[Q], cands[P] with P = gptr[Q]; group q scores
+ * its source u = sources[q] against each candidate v = cands[j], j in [gptr[q], gptr[q + 1]). Repeated
+ * sources, repeated candidates, v == u and groups without candidates are legal.
+ * B[x] is the current row of x after `iterations_run` iterations (the slot rule of
+ * ppr_grank_plan_fetch_slab; stored ids decoded to keys, undecodable ones skipped; the row length
+ * clamped to [0, L]); len(x) = its decodable entries.
+ * Outputs, each indexed by the candidate position j except out_slen (by q); each is optional: NULL =
+ * not computed and not written.
+ *   out_fwd[j]     the score of key v in B[u], bit for bit, +0.0 when v is absent
+ *   out_bwd[j]     the score of key u in B[v], bit for bit, +0.0 when u is absent
+ *   out_hit[j]     bit 0: v is a key of B[u]; bit 1: u is a key of B[v] (zero scores are legal keys,
+ *                  so a score cannot tell absent from zero)
+ *   out_rank[j]    the 0-based position of v among the decodable entries of B[u] ordered by (score
+ *                  descending, key ascending), -1 when v is absent (scores are >= +0, so their bit
+ *                  patterns order like the values)
+ *   out_common[j]  |keys(B[u]) & keys(B[v])|
+ *   out_dot[j]     over the common keys k, X = sum floor(fl(B[u][k] * B[v][k]) * 2^93), each term one
+ *                  fp64 multiply, the sum an exact integer; the result is X * 2^-93 rounded to nearest
+ *                  even once. The sum has no order: dot(u, v) and dot(v, u) have the same bits. Every
+ *                  GRank row sums to <= 1 (the bound ppr_grank_plan_rquery states), so the products sum
+ *                  to <= 1 and X < 2^95 fits the 96-bit sum. An MC plan's scores are not bounded by 1
+ *                  (its totals reach deg / d), so the sum could overflow: MC plans are refused.
+ *   out_slen[q] = len(u), out_clen[j] = len(v): with out_common they give the Jaccard, with
+ *                  dot(u, u) and dot(v, v) the cosine.
+ * Two work classes, chosen per call: with out_common and out_dot both NULL (lookup class) no row is
+ * walked for a pair -- v is searched in the one 1/64 segment of B[u] its hash range names, u in B[v] the
+ * same way; otherwise (overlap class) B[u] is held in LDS per group task and the candidates' rows are
+ * streamed against it. The result depends only on the slab and the arguments: not on the class, the
+ * tier, how groups were split or chunked, the knobs or the order of groups or candidates. No float
+ * atomics; every output position is fixed by j alone.
+ * Host pointers; synchronous on the plan's stream; writes nothing into the slabs or the plan's top-K
+ * output.
+ * Refusals, all decided on the host before any kernel starts, in this order; they leave every output
+ * untouched (st is cleared): PPR_ERR_ARG (a null plan, an MC plan, iterations_run < 0, null gptr,
+ * Q < 0; then gptr[0] != 0 or a decreasing gptr; then null sources with Q > 0; then null cands with
+ * P > 0; then unknown flag bits -- none is defined; then every output pointer NULL), PPR_ERR_RANGE (Q or
+ * P above 2^31 - 1), PPR_ERR_SOURCE (a source or candidate outside [0, n)). A call with Q == 0, or with
+ * P == 0 and no out_slen, returns PPR_OK without a launch.
+ * Stats: pairs = P, groups = Q, lookup_pairs + overlap_pairs = P (the class of the call),
+ * entries_read = row ids the kernels read; wave_groups / wg_groups / split_groups = the groups of an
+ * overlap-class call by tier (every group has exactly one; all 0 in the lookup class).
+ * algo_bytes = the bytes the algorithm has to move, with len the stored length of a row. Both classes:
+ * per pair the requested outputs (fwd 8, bwd 8, hit 1, rank 4, common 4, dot 8, clen 4) + 4 for the
+ * candidate id; per group 4 for the source id and, with out_slen, 4 + 4 len(u) (the ids are decoded to
+ * be counted). Overlap class: per group task 12 len(u) + 128 for the row and its range index, + 2 len(u)
+ * with out_rank; per pair 4 len(v) for the ids, + 8 common for the scores of the hits with out_dot.
+ * Lookup class: per pair 8 for the two range-index reads + 4 for the pair's group index + 4 per id of
+ * the two probed segments + 8 per hit score, + 4 len(v) with out_clen; with out_rank 14 len(u) + 128
+ * once per group (ids, scores, the range index, the 2-byte ranks written) and 2 per forward hit. */
+typedef struct ppr_pairs_stats {
+  double device_ms;          /* HIP events around the kernels; uploads and downloads excluded */
+  int64_t pairs, groups;
+  int64_t lookup_pairs, overlap_pairs;
+  int64_t entries_read;
+  int64_t algo_bytes;        /* see above */
+  int64_t wave_groups, wg_groups, split_groups;
+  int32_t chunks; int32_t reserved;
+} ppr_pairs_stats;
+int ppr_grank_plan_pairs(ppr_plan* p, int32_t iterations_run, int64_t Q, const int64_t* gptr,
+                         const int32_t* sources, const int32_t* cands, uint32_t flags,
+                         double* out_fwd, double* out_bwd, uint8_t* out_hit, int32_t* out_rank,
+                         int32_t* out_common, double* out_dot, int32_t* out_slen, int32_t* out_clen,
+                         ppr_pairs_stats* st);
+
 /* ---- MCCompletePathV2 (ppr::mccompletepathv2, include/mccompletepathv2.h:182-258) ----
  * `walks` is the reference's `iterations` (R): floor(R*d) walks per walk-set node. The walks use
  * counter-based Philox4x32-10 keyed by `seed` (the reference seeds a global mt19937 from
